@@ -20,8 +20,12 @@ opt-out that leaves unlabelled rows unread is timed on one step afterwards (`val
 
 The transformer forward/backward itself is outside the path (stock PyTorch-ROCm); the metric string says so, and
 `--detail` measures a model-in-the-loop step separately.  Scaling is STRONG: the global batch of 4096 sequences is fixed and
-sharded across ranks.  Rank 0 prints ONE JSON line of < 4 KB (`split_line`: the driver's keys + roofline + cpu_baseline +
-weight_sync) and writes everything else it measured to `--detail-out` (default gpurun_out/bench_detail.json).
+sharded across ranks.  Rank 0 prints ONE JSON line of < 4 KB (`split_line`: the driver's keys + roofline, + cpu_baseline and
+weight_sync with `--full`).
+
+A plain run sets up, warms up, times `--steps` steps, writes the last step's outputs if `--dump-outputs DIR` is given and prints
+the line.  Everything else - the opt-out steps, the CPU baseline, the weight-sync probe, the live PMC passes, the pinned upload and
+the detail file (`--detail-out`) - runs with `--full` only; `--detail` (the side measurements) implies `--full`.
 """
 
 from __future__ import annotations
@@ -67,6 +71,12 @@ def parse_args():
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--workload", default=os.environ.get("PRL_BENCH_WORKLOAD", "7b_grpo_bs4096_seq8192"), choices=list(WORKLOADS))
     p.add_argument("--logits-mode", default=os.environ.get("PRL_BENCH_LOGITS_MODE", "fused"), choices=["fused", "two_pass"])
+    p.add_argument("--full", action="store_true",
+                   help="also run everything the headline figure does not need: the opt-out steps (value_skip_unlabelled), the CPU baseline, "
+                        "the weight-sync probe, the live PMC passes, the pinned upload; writes the detail file (--detail-out)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, a seeded "
+                        "sample of the large arrays, at most 64 MB in all; rank 0's shard)")
     p.add_argument("--detail", action="store_true",
                    help="also run the side measurements (MFMA head roofline, model-in-the-loop step, reference-policy head, preprocessor loop, "
                         "configs[1] pipeline, transport) - they go to the detail file, never into the printed line")
@@ -94,7 +104,9 @@ def parse_args():
                    help="comma-separated thread counts: time ONLY the cpu_baseline loss leg at each count and exit (no GPU work)")
     p.add_argument("--backend", default=os.environ.get("PRL_BENCH_BACKEND", "nccl"), choices=["nccl", "gloo"],
                    help="gloo + PRL_BENCH_SHARE_DEVICE=1 runs N ranks on ONE GPU (dry run of the N > 1 logic)")
-    return p.parse_args()
+    args = p.parse_args()
+    args.full = args.full or args.detail
+    return args
 
 
 class EventTimer:
@@ -936,7 +948,56 @@ def _pick(d: dict | None, keys) -> dict | None:
     return None if d is None else {k: d[k] for k in keys if k in d}
 
 
-def split_line(full: dict, detail_path: str) -> tuple[dict, dict]:
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20240607
+DUMP_GRAD_ELEMENTS = 1 << 22  # 16 MB of fp32 d loss / d logits
+DUMP_TOKENS = 1 << 18  # token positions sampled from every step-long array
+
+
+def _seeded_index(n: int, k: int, gen: torch.Generator) -> torch.Tensor:
+    """Every index when n <= k, else k sorted indices drawn uniformly (with replacement) from [0, n) by `gen`."""
+    if n <= k:
+        return torch.arange(n, dtype=torch.int64)
+    return torch.randint(0, n, (k,), generator=gen, dtype=torch.int64).sort().values
+
+
+def _as_dump_array(t: torch.Tensor) -> np.ndarray:
+    """fp32 / fp64 stay as they are; integers (exact below 2^53) and bf16 become fp64 / fp32."""
+    t = t.detach()
+    if t.dtype in (torch.float32, torch.float64):
+        return t.cpu().numpy()
+    if t.is_floating_point():
+        return t.float().cpu().numpy()
+    return t.to(torch.float64).cpu().numpy()
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, stats: torch.Tensor, grad_logits: torch.Tensor, step) -> dict[str, int]:
+    """`--dump-outputs`: what the timed path handed its caller in the last timed step - the loss and the 32 statistics of `finish`,
+    d loss / d logits of the last micro-batch, the packed step batch of `preprocess` and the per-token log-probs / entropies the
+    logits kernel wrote - as DIR/<name>.npy.  The large arrays are sampled at positions drawn from a fixed seed (same arguments =>
+    same positions), so two builds compare output for output.  Returns {name: bytes}."""
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+    dev = grad_logits.device
+    arrays: dict[str, np.ndarray] = {"loss": _as_dump_array(loss), "stats": _as_dump_array(stats)}
+    g = grad_logits.reshape(-1)
+    arrays["grad_logits_last_micro_batch_sample"] = _as_dump_array(g[_seeded_index(g.numel(), DUMP_GRAD_ELEMENTS, gen).to(dev)])
+    n_tok = int(step.step_batch.input_ids.numel())
+    tok = _seeded_index(n_tok, DUMP_TOKENS, gen).to(dev)
+    per_token = [(f"batch_{name}", t) for name, t in step.step_batch.tensors()]
+    per_token += [("new_logprobs", step.buffers.new_logprobs), ("entropy", step.buffers.entropy)]
+    for name, t in per_token:
+        if t.numel() == n_tok:  # step-long [1, T] columns (per-sequence tables are not per token and stay out)
+            arrays[f"{name}_sample"] = _as_dump_array(t.reshape(-1)[tok])
+    sizes = {name: int(a.nbytes) for name, a in arrays.items()}
+    assert sum(sizes.values()) <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {sum(sizes.values())} bytes (limit {DUMP_LIMIT_BYTES})"
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return sizes
+
+
+def split_line(full: dict, detail_path: str | None) -> tuple[dict, dict]:
     """(the ONE printed line, the detail file's content).  The line carries exactly the driver's contract - scalars where the contract
     has scalars, `cpu_baseline.cores` an int, at most LINE_LIMIT_BYTES - and the path of the detail file; everything else that was measured
     (per-kernel table, CPU legs, side measurements) is in the detail file only.  Pure function of `full`: tests/test_bench_line.py."""
@@ -1073,13 +1134,15 @@ def main():
     rag = rag_h.to(dev)
     torch.cuda.synchronize()
     t_h2d = time.perf_counter() - t_h2d
-    rag_pinned = rag_h.pin_memory()
-    torch.cuda.synchronize()
-    t_h2d_pinned = time.perf_counter()
-    rag = rag_pinned.to(dev)
-    torch.cuda.synchronize()
-    t_h2d_pinned = time.perf_counter() - t_h2d_pinned
-    del rag_pinned
+    t_h2d_pinned = None
+    if args.full:
+        rag_pinned = rag_h.pin_memory()
+        torch.cuda.synchronize()
+        t_h2d_pinned = time.perf_counter()
+        rag = rag_pinned.to(dev)
+        torch.cuda.synchronize()
+        t_h2d_pinned = time.perf_counter() - t_h2d_pinned
+        del rag_pinned
     h2d_bytes = sum(t.numel() * t.element_size() for t in (rag.tokens, rag.labels, rag.logprobs, rag.seq_off, rag.lp_off, rag.reward)
                     + ((rag.ref_logprobs,) if rag.ref_logprobs is not None else ()))
     n_seq = rag.n_seqs
@@ -1145,7 +1208,7 @@ def main():
                 dist.all_reduce(gb)
             if ctx:
                 ctx.__exit__(None, None, None)
-        return loss, stats
+        return loss, stats, step
 
     def barrier():
         if world > 1:
@@ -1157,7 +1220,8 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, stats = one_step(True, timer=main_timer)
+        last = None  # the previous step's buffers go before the next step allocates its own
+        loss, stats, last = one_step(True, timer=main_timer)
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -1165,6 +1229,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, stats, grad_logits, last)
+    del last
     stats_host = stats.cpu().tolist()
     assert np.isfinite(stats_host[0]), "non-finite loss in the benchmark step"
     assert int(stats_host[2]) == bs, f"step covered {int(stats_host[2])} sequences, expected {bs}"
@@ -1199,7 +1266,7 @@ def main():
 
     # ---- the opt-out (HotPathStep's default, skip_unlabelled=True), timed separately on a few steps: never `value` ----
     optout = None
-    if args.skip_unlabelled_steps > 0:
+    if args.full and args.skip_unlabelled_steps > 0:
         t_opt = EventTimer()  # (no warm-up of its own: same kernels, same buffers, the flag is a launch argument)
         barrier()
         t1 = time.perf_counter()
@@ -1235,13 +1302,13 @@ def main():
     skipped: dict[str, str] = {}
 
     def fits(name: str, estimate_s: float) -> bool:
-        """Optional legs of a DEFAULT run stay inside --budget-s (the driver's lease is shared with the tests and the smoke)."""
+        """Optional legs of a --full run stay inside --budget-s (the driver's lease is shared with the tests and the smoke)."""
         if args.detail or time.perf_counter() - T_START + estimate_s <= args.budget_s:
             return True
         skipped[name] = f"not run: {time.perf_counter() - T_START:.0f} s spent, ~{estimate_s:.0f} s needed, budget {args.budget_s:.0f} s (--detail or --budget-s lifts it)"
         return False
 
-    cpu_base = None if (args.no_cpu_baseline or world != 1) else cpu_baseline(seq_length, vocab)
+    cpu_base = None if (not args.full or args.no_cpu_baseline or world != 1) else cpu_baseline(seq_length, vocab)
 
     # The weight-sync probe creates its own RCCL communicator; a hang there must not cost the
     # benchmark line, so a watchdog prints the line without it and ends the process.
@@ -1253,7 +1320,7 @@ def main():
         torch.cuda.empty_cache()
 
     wsync = None
-    if world == 1 and not args.no_weight_sync and os.environ.get("PRL_BENCH_WSYNC", "1") != "0":
+    if args.full and world == 1 and not args.no_weight_sync and os.environ.get("PRL_BENCH_WSYNC", "1") != "0":
         # (never skipped for time: "trainer->actor weight-sync ms" is half of BASELINE.json's metric)  one GPU: the only trainer -> actor layout is colocated; hand the 7B / 0.5B parameter set to a
         # second process on this GPU over HIP IPC (request-to-ack of send_weight_update, median of 5)
         release_step_buffers()
@@ -1267,7 +1334,7 @@ def main():
         except Exception as e:  # noqa: BLE001 - the probe must never take the benchmark line down
             wsync = {"error": f"{type(e).__name__}: {e}"}
 
-    if (rank == 0 and world == 1 and dom == "fused_logits_loss" and (seq_length, vocab) == (8192, 152064) and not args.no_live_pmc
+    if (args.full and rank == 0 and world == 1 and dom == "fused_logits_loss" and (seq_length, vocab) == (8192, 152064) and not args.no_live_pmc
             and os.environ.get("PRL_BENCH_LIVE_PMC", "1") != "0" and fits("live_pmc", 45)):
         release_step_buffers()
         try:
@@ -1355,7 +1422,7 @@ def main():
                               "torch_distributed": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(), "devices_visible": torch.cuda.device_count(),
                                                      "distinct_devices": distinct_devices, "rccl_comm_size": (wsync or {}).get("rccl_comm_size"),
                                                      "share_device_dry_run": share_device} if world > 1 else None),
-                              "h2d_ragged_input": {"bytes": h2d_bytes, "ms": 1e3 * t_h2d, "ms_pinned": 1e3 * t_h2d_pinned,
+                              "h2d_ragged_input": {"bytes": h2d_bytes, "ms": 1e3 * t_h2d, "ms_pinned": None if t_h2d_pinned is None else 1e3 * t_h2d_pinned,
                                                    "note": "one step's ragged rollouts, pageable vs page-locked host memory; not part of value"}},
             "roofline": roofline,
             "value_skip_unlabelled": optout,
@@ -1367,17 +1434,18 @@ def main():
             "wall_s": time.perf_counter() - T_START,
             **side,
         })
-        line, detail = split_line(full, args.detail_out)
-        out = ROOT / args.detail_out
-        try:
-            out.parent.mkdir(parents=True, exist_ok=True)
-            out.write_text(json.dumps(detail, indent=1) + "\n")
-        except OSError as e:  # a read-only tree must not cost the line
-            line["detail"] = f"not written: {e}"
+        line, detail = split_line(full, args.detail_out if args.full else None)
+        if args.full:  # a plain run writes no detail file
+            out = ROOT / args.detail_out
+            try:
+                out.parent.mkdir(parents=True, exist_ok=True)
+                out.write_text(json.dumps(detail, indent=1) + "\n")
+            except OSError as e:  # a read-only tree must not cost the line
+                line["detail"] = f"not written: {e}"
         print(json.dumps(line), flush=True)
 
     force = os.environ.get("PRL_BENCH_FORCE_WSYNC") == "1"  # dry runs: exercise the probe's error handling under gloo
-    if world > 1 and (args.backend == "nccl" or force) and not args.no_weight_sync and os.environ.get("PRL_BENCH_WSYNC", "1") != "0":
+    if args.full and world > 1 and (args.backend == "nccl" or force) and not args.no_weight_sync and os.environ.get("PRL_BENCH_WSYNC", "1") != "0":
         import threading
 
         done = threading.Event()

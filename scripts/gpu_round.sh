@@ -1,6 +1,6 @@
 #!/bin/bash
-# One GPU-box session: the whole -m gpu suite, smoke, the DRIVER's bench command (default legs only), rocprofv3 kernel stats of the same
-# timed region, then `bench.py --detail` (side measurements -> detail file) and the other two BASELINE workloads.
+# One GPU-box session: the whole -m gpu suite, smoke, the bench command with every leg of the line (--full), rocprofv3 kernel stats of
+# the same timed region, then `bench.py --detail` (side measurements -> detail file) and the other two BASELINE workloads.
 # Everything is logged under gpurun_out/<tag>/.   usage: gpurun --timeout 3000 -- 'bash scripts/gpu_round.sh r06a [skip-tests]'
 set -u
 TAG=${1:-round}
@@ -15,8 +15,8 @@ if [ "${2:-}" != "skip-tests" ]; then
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
   echo "smoke exit $?" | tee -a $OUT/smoke.log; tail -2 $OUT/smoke.log
 fi
-# exactly what the driver runs at round end
-( time timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --detail-out $OUT/bench_default_detail.json ) > $OUT/bench_default.log 2> $OUT/bench_default.err
+# the headline command plus every leg of the line (opt-out steps, cpu_baseline, weight_sync, live PMC) and the detail file
+( time timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --detail-out $OUT/bench_default_detail.json ) > $OUT/bench_default.log 2> $OUT/bench_default.err
 echo "bench exit $?" | tee -a $OUT/bench_default.err
 tail -4 $OUT/bench_default.err
 python - "$OUT" <<'PY'
@@ -34,7 +34,7 @@ find $OUT/prof -name "*kernel_trace.csv" -delete
 grep '^{' $OUT/rocprof.log | tail -1 > $OUT/bench_under_rocprof.json
 if [ "${3:-}" == "no-detail" ]; then exit 0; fi
 # side measurements (never on the line): MFMA head, model-in-the-loop step, reference-policy head, preprocessor loop, configs[1] pipeline, transport
-( time timeout 1500 python bench.py --steps 3 --warmup 1 --detail --detail-out $OUT/bench_detail.json ) > $OUT/bench_detail.log 2> $OUT/bench_detail.err
+( time timeout 1500 python bench.py --steps 3 --warmup 1 --full --detail --detail-out $OUT/bench_detail.json ) > $OUT/bench_detail.log 2> $OUT/bench_detail.err
 echo "bench --detail exit $?"
 python - "$OUT" <<'PY'
 import json, sys
@@ -56,8 +56,8 @@ pl = d.get("pipeline") or {}
 print(" pipeline", {k: pl.get(k) for k in ("samples_per_s", "s_per_step", "busy_frac", "error")})
 PY
 # the other two BASELINE workloads (configs[4]: 32B, KL on; configs[1]: 0.5B)
-( time timeout 600 python bench.py --workload 32b_grpo_kl_bs4096_seq8192 --steps 2 --warmup 1 --detail-out $OUT/bench_32b_detail.json ) > $OUT/bench_32b.log 2> $OUT/bench_32b.err
+( time timeout 600 python bench.py --workload 32b_grpo_kl_bs4096_seq8192 --steps 2 --warmup 1 --full --detail-out $OUT/bench_32b_detail.json ) > $OUT/bench_32b.log 2> $OUT/bench_32b.err
 echo "bench 32b exit $?"
-( time timeout 300 python bench.py --workload 0p5b_grpo_bs512_seq2048 --steps 5 --warmup 2 --detail-out $OUT/bench_0p5b_detail.json ) > $OUT/bench_0p5b.log 2> $OUT/bench_0p5b.err
+( time timeout 300 python bench.py --workload 0p5b_grpo_bs512_seq2048 --steps 5 --warmup 2 --full --detail-out $OUT/bench_0p5b_detail.json ) > $OUT/bench_0p5b.log 2> $OUT/bench_0p5b.err
 echo "bench 0p5b exit $?"
 grep -h '^{' $OUT/bench_32b.log $OUT/bench_0p5b.log | cut -c1-600

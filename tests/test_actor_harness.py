@@ -5,7 +5,6 @@ LearnerStep) is tests/test_gpu_actor_flow.py."""
 
 import asyncio
 import json
-import os
 import sys
 import types
 from pathlib import Path
@@ -44,17 +43,25 @@ def test_dataset_plugin_returns_what_the_reference_loader_returns():
     assert load_problems(["other"]) == []
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/pipelinerl"), reason="the reference checkout is only present in the build container")
-def test_harness_drives_the_references_own_dataset_plugin(streams, tmp_path):
-    """`cfg.dataset_loader` pointing INTO the reference: its `load_problems` supplies the problems."""
-    sys.path.insert(0, str(GOLDEN))
-    try:
-        from make_guessing_golden import import_reference_guessing
+def _recorded_reference_guessing() -> types.ModuleType:
+    """A stand-alone module whose `load_problems` returns what the reference's own loader returned, as recorded in
+    tests/golden/guessing_problems.json (tests/golden/make_guessing_golden.py): splits concatenate in argument order,
+    unknown names are ignored."""
+    g = json.loads((GOLDEN / "guessing_problems.json").read_text())
+    assert g["concatenates_in_argument_order"] and g["unknown_name_is_ignored"]
 
-        ref = import_reference_guessing()
-    finally:
-        sys.path.remove(str(GOLDEN))
-    sys.modules["reference_guessing"] = ref
+    def load_problems(dataset_names, **_params):
+        return [{"answer": a, "dataset": name, "domain": g["domain"]} for name in dataset_names for a in g["answers"].get(name, [])]
+
+    m = types.ModuleType("reference_guessing")
+    m.load_problems = load_problems
+    return m
+
+
+def test_harness_drives_the_references_own_dataset_plugin(streams, tmp_path):
+    """`cfg.dataset_loader` pointing at a module outside the test plugins, by dotted path: the reference's `load_problems`
+    (its recorded output) supplies the problems."""
+    sys.modules["reference_guessing"] = _recorded_reference_guessing()
     try:
         from pipelinerl_amd.actor_harness import ActorHarness
         from plugins.guessing_plugin import ScriptedLLM

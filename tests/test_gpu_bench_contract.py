@@ -12,20 +12,20 @@ pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def _run(extra, tmp_path, timeout=900):
+def _run(extra, tmp_path, timeout=900, steps=2):
     detail = tmp_path / "bench_detail.json"
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--detail-out", str(detail), *extra],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny", "--steps", str(steps), "--warmup", "1", "--detail-out", str(detail), *extra],
                          capture_output=True, text=True, timeout=timeout, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
     assert out.stdout.rstrip().splitlines()[-1] == lines[0]  # the line is the LAST thing on stdout (the driver parses the tail)
-    return lines[0], json.loads(detail.read_text())
+    return lines[0], (json.loads(detail.read_text()) if detail.exists() else None)
 
 
 def test_bench_json_contract(libprl, cuda_device, tmp_path):
-    """The default invocation: one line under 4 KB with the driver's keys, `roofline` and `cpu_baseline` scalar-valued, the rest in the detail file."""
-    text, full = _run([], tmp_path)
+    """`--full`: one line under 4 KB with the driver's keys, `roofline` and `cpu_baseline` scalar-valued, the rest in the detail file."""
+    text, full = _run(["--full"], tmp_path)
     assert len(text.encode()) < 4096
     d = json.loads(text)
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
@@ -71,7 +71,7 @@ def test_bench_json_contract(libprl, cuda_device, tmp_path):
 
 def test_bench_detail_side_measurements(libprl, cuda_device, tmp_path):
     """`--detail`: the side measurements run and land in the detail file; the printed line keeps its shape."""
-    text, d = _run(["--detail"], tmp_path, timeout=1500)
+    text, d = _run(["--full", "--detail"], tmp_path, timeout=1500)
     assert len(text.encode()) < 4096 and "pipeline" not in json.loads(text)
     m = d["roofline_mfma"]  # the MFMA-bound fused head, a second roofline object
     assert "error" not in m, m
@@ -103,8 +103,38 @@ def test_bench_detail_side_measurements(libprl, cuda_device, tmp_path):
     assert pl["overlap"]["pipelined_s_per_step"] > 0 and sum(pl["lag_optimizer_steps_histogram"].values()) > 0
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(libprl, cuda_device, tmp_path):
+    """A plain run: the headline keys, `--steps` timed steps, none of the --full legs, no detail file; `--dump-outputs` writes the last
+    step's outputs as float32 / float64 .npy files (<= 64 MB), the same for the same arguments."""
+    import numpy as np
+
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        out.mkdir()
+        text, detail = _run(["--dump-outputs", str(out / "outputs")], out, steps=3)
+        d = json.loads(text)
+        assert detail is None and d["detail"] is None
+        for key, typ in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str)):
+            assert type(d[key]) is typ, key
+        assert d["steps"] == 3 and d["roofline"]["launches"] == 3 * d["config"]["global_batch"] and d["higher_is_better"] is True
+        assert abs(d["value"] - d["config"]["global_batch"] / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+        assert d["cpu_baseline"] is None and d["weight_sync"] is None and d["value_skip_unlabelled"] is None
+        files = sorted((out / "outputs").glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrays = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert {"loss", "stats", "grad_logits_last_micro_batch_sample", "batch_input_ids_sample", "batch_advantages_sample", "new_logprobs_sample"} <= set(arrays)
+        assert arrays["stats"].shape == (32,) and arrays["stats"][2] == d["config"]["global_batch"] and arrays["stats"][0] == d["loss"]
+        assert np.isfinite(arrays["grad_logits_last_micro_batch_sample"]).all() and np.abs(arrays["grad_logits_last_micro_batch_sample"]).max() > 0
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name, a in dumps[0].items():
+        np.testing.assert_allclose(dumps[1][name], a, rtol=1e-5, atol=1e-7, err_msg=name)
+
+
 @pytest.mark.parametrize("world", [2, 8])
-def test_bare_multi_gpu_invocation_becomes_n_ranks(libprl, cuda_device, world):
+def test_bare_multi_gpu_invocation_becomes_n_ranks(libprl, cuda_device, world, tmp_path):
     """`python bench.py --gpus N` with no launcher re-executes itself as N ranks (here all on this GPU over gloo, the dry-run mode)
     and the line's `n_gpus` comes from the process group, not from argv.  N = 8 is the driver's scaling run: the batch splits into
     whole groups per rank, every rank shards / packs / runs its share, the statistics all-gather closes the step."""
@@ -112,13 +142,14 @@ def test_bare_multi_gpu_invocation_becomes_n_ranks(libprl, cuda_device, world):
 
     env = {**os.environ, "PRL_BENCH_SHARE_DEVICE": "1"}
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
+    detail = tmp_path / "bench_detail_ranks.json"
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--backend", "gloo", "--workload", "tiny", "--steps", "1", "--warmup", "0",
-                          "--no-weight-sync", "--detail-out", "gpurun_out/bench_detail_2ranks.json"], capture_output=True, text=True, timeout=900, cwd=str(ROOT), env=env)
+                          "--full", "--no-weight-sync", "--detail-out", str(detail)], capture_output=True, text=True, timeout=900, cwd=str(ROOT), env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
     assert len(lines[0]) < 4096
-    td = json.loads((ROOT / "gpurun_out" / "bench_detail_2ranks.json").read_text())["config_detail"]["torch_distributed"]
+    td = json.loads(detail.read_text())["config_detail"]["torch_distributed"]
     assert d["n_gpus"] == world and td["world_size"] == world and td["backend"] == "gloo" and td["share_device_dry_run"] is True and td["distinct_devices"] == 1
     assert d["config"]["parallelism"] == f"dp{world}" and d["config"]["backend"] == "gloo" and d["config"]["distinct_devices"] == 1 and d["cpu_baseline"] is None

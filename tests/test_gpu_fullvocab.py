@@ -19,6 +19,7 @@ import torch
 
 from oracle import rl_loss as orl
 
+import grad_checks as gc
 from helpers import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -112,7 +113,19 @@ def _launch_fused(lib, dev, logits_t, batch, cfg_name, inplace):
     return nlp, ent, grad, lib.prl_last_fused_kernel().decode()
 
 
-def _check_against_oracle(nlp, ent, grad, want, g64, dtype, cfg_name):
+def _check_per_entry(got, logits, batch, want, dtype, cfg_name, kernel=None):
+    """d logits entry by entry against the size of each entry's own terms (grad_checks): the max norm below sees
+    only the ~0.2 % of a full-vocabulary row that is larger than its tolerance."""
+    rid, g, gh = gc.token_rows(batch["input_ids"], want["g_nlp"], want["g_ent"])
+    V = logits.shape[-1]
+    res = gc.dlogits_error(got[0], logits[0], rid, g, gh, CONFIGS[cfg_name]["temperature"],
+                           out_rounding=gc.BF16_ROUNDING if dtype == "bf16" else 0.0,
+                           regions=gc.regions_of_kernel(kernel, V, (V * (4 if dtype == "f32" else 2)) % 16 == 0) if kernel else None)
+    print(f"[dlogits] V={V} {cfg_name} {dtype} {kernel}: {res.err:.3e} (bound {gc.DLOGITS_BOUND['randn_spiky']:.1e})")
+    assert res.ok(gc.DLOGITS_BOUND["randn_spiky"]), f"{kernel}: {res}"
+
+
+def _check_against_oracle(nlp, ent, grad, want, g64, dtype, cfg_name, logits=None, batch=None, kernel=None):
     g_nlp, g_ent = nlp.cpu().numpy(), ent.cpu().numpy()
     assert g_nlp[0, 0] == 0 and g_ent[0, 0] == 0
     np.testing.assert_allclose(g_nlp[:, 1:], want["new_logprobs"], rtol=FP_TOL, atol=2e-5)
@@ -127,6 +140,7 @@ def _check_against_oracle(nlp, ent, grad, want, g64, dtype, cfg_name):
     if cfg_name == "grpo_clip":
         assert set(range(19, 29)) <= set(zero_rows.tolist()), "the crafted clipped rows must have zero gradient"
     assert np.count_nonzero(got) > 0
+    _check_per_entry(got, logits, batch, want, dtype, cfg_name, kernel)
 
 
 @pytest.mark.parametrize("vocab,cfg_name,dtype,inplace", list(itertools.product(
@@ -145,7 +159,7 @@ def test_default_fused_dispatch_vs_oracle(libprl, cuda_device, monkeypatch, voca
         assert kernel.startswith("fused_logits_loss_keep_kernel<F32,1024,2,16,9"), kernel
     else:
         assert kernel.startswith("fused_logits_loss_kernel<BF16,512"), kernel
-    _check_against_oracle(nlp, ent, grad, want, g64, dtype, cfg_name)
+    _check_against_oracle(nlp, ent, grad, want, g64, dtype, cfg_name, logits, batch, kernel)
 
 
 @pytest.mark.parametrize("dtype,variant", list(itertools.product(["f32", "bf16"], [0, 4, 6, 21])))
@@ -160,7 +174,7 @@ def test_every_fused_variant_vs_oracle(libprl, cuda_device, monkeypatch, variant
     # a bf16 row is 19 008 sixteen-byte vectors: the 25-vector-per-lane head of the row-resident shape does not fit and falls back
     if variant == 21 and dtype == "f32":
         assert "keep_kernel" in kernel, kernel
-    _check_against_oracle(nlp, ent, grad, want, g64, dtype, "kl_ent_temp")
+    _check_against_oracle(nlp, ent, grad, want, g64, dtype, "kl_ent_temp", logits, batch, kernel)
 
 
 def test_short_and_unaligned_rows_fall_back(libprl, cuda_device, monkeypatch):
@@ -171,7 +185,7 @@ def test_short_and_unaligned_rows_fall_back(libprl, cuda_device, monkeypatch):
         logits, batch, want, g64 = _case(V, 40, "kl_ent_temp", "f32")
         nlp, ent, grad, kernel = _launch_fused(libprl, cuda_device, torch.from_numpy(logits).to(cuda_device), batch, "kl_ent_temp", False)
         assert kernel.startswith("fused_logits_loss_kernel<F32"), (V, kernel)
-        _check_against_oracle(nlp, ent, grad, want, g64, "f32", "kl_ent_temp")
+        _check_against_oracle(nlp, ent, grad, want, g64, "f32", "kl_ent_temp", logits, batch, kernel)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
@@ -306,6 +320,12 @@ def test_logits_backward_full_vocab_vs_fp64(libprl, cuda_device, vocab, dtype):
         want[:, :-1] = 0.5 * (g[:, 1:, None].double() * (onehot - p) - gh[:, 1:, None].double() * p * (logp + H)) / temp
         tol = 1e-4 if dtype == torch.float32 else 1e-2
         assert rel_err(grad.double().cpu().numpy(), want.cpu().numpy()) <= tol
+        rid, rg, rgh = gc.token_rows(ids.cpu().numpy(), 0.5 * g[:, 1:].cpu().numpy(), 0.5 * gh[:, 1:].cpu().numpy())
+        res = gc.dlogits_error(grad.float().cpu().numpy().reshape(B * L, V), logits.float().cpu().numpy().reshape(B * L, V), rid, rg, rgh,
+                               temp, out_rounding=gc.BF16_ROUNDING if dtype == torch.bfloat16 else 0.0,
+                               regions=gc.kernel_regions(V, 4 if dtype == torch.float32 else 8, 256, 4))
+        print(f"[dlogits] K1 backward V={V} {dtype} inplace={inplace}: {res.err:.3e} (bound {gc.DLOGITS_BOUND['k1_random_g']:.1e})")
+        assert res.ok(gc.DLOGITS_BOUND["k1_random_g"]), str(res)
         assert torch.count_nonzero(grad[0, 4]).item() == 0 and torch.count_nonzero(grad[:, -1]).item() == 0
         # forward values against fp64 too
         w_nlp = logp.gather(2, ids[:, 1:, None])[..., 0]

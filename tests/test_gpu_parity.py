@@ -11,6 +11,7 @@ import torch
 from oracle import preprocess as opre
 from oracle import rl_loss as orl
 
+import grad_checks as gc
 from helpers import (
     PREPROCESS_CASES,
     RL_STEP_CASES,
@@ -181,6 +182,13 @@ def test_logits_backward_vs_autograd(libprl, cuda_device, dtype):
     ((r_nlp * g[:, 1:]).sum() * 0.5 + (r_ent * gh[:, 1:]).sum() * 0.5).backward()
     tol = 1e-4 if dtype == torch.float32 else 2e-2
     assert rel_err(grad.float().cpu().numpy(), x.grad.cpu().numpy()) <= tol
+    # entry by entry against the fp64 closed form (grad_checks): V = 1031 with stride 1031 is the all-scalar walk
+    rid, rg, rgh = gc.token_rows(ids.cpu().numpy(), 0.5 * g[:, 1:].cpu().numpy(), 0.5 * gh[:, 1:].cpu().numpy())
+    res = gc.dlogits_error(grad.float().cpu().numpy().reshape(B * L, V), logits.float().cpu().numpy().reshape(B * L, V), rid, rg, rgh,
+                           temp, out_rounding=gc.BF16_ROUNDING if dtype == torch.bfloat16 else 0.0,
+                           regions=gc.kernel_regions(V, 4 if dtype == torch.float32 else 8, 256, 4, vec_ok=False))
+    print(f"[dlogits] K1 backward V={V} {dtype}: {res.err:.3e} (bound {gc.DLOGITS_BOUND['k1_random_g']:.1e})")
+    assert res.ok(gc.DLOGITS_BOUND["k1_random_g"]), str(res)
 
 
 @pytest.mark.parametrize("name", PREPROCESS_CASES)
@@ -420,6 +428,10 @@ def test_full_size_properties(libprl, cuda_device):
                                                    _lib.current_stream_ptr(cuda_device)))
     rows = grad[0].double().sum(-1)
     assert rows.abs().max().item() < 1e-3
+    # the relative form: 1e-3 absolute with g ~ 1 allows a row to lose 0.1 % of its mass
+    rel = rows.abs() / grad[0].double().abs().sum(-1).clamp_min(1e-300)
+    print(f"[rowsum] max |sum d logits| / sum |d logits| = {rel.max().item():.3e} (bound {gc.ROWSUM_BOUND:.1e})")
+    assert rel.max().item() <= gc.ROWSUM_BOUND
     zero_rows = (g[0, 1:] == 0).nonzero().flatten()
     assert torch.count_nonzero(grad[0, zero_rows]).item() == 0
     assert torch.count_nonzero(grad[0, -1]).item() == 0
@@ -490,6 +502,19 @@ def test_fused_kernel_variants_agree(libprl, cuda_device, variant, monkeypatch):
     # block-size changes alter the reduction tree of the online softmax: fp32-rounding-level differences
     assert torch.allclose(n0, n1, rtol=1e-6, atol=1e-6) and torch.allclose(e0, e1, rtol=1e-5, atol=1e-6)
     assert rel_err(g1.cpu().numpy(), g0.cpu().numpy()) <= 1e-5
+    # each variant entry by entry against the fp64 closed form, with the oracle's token gradients for the kernel's own
+    # log-probs / entropies (the max norm above sees ~0.2 % of a full-vocabulary row)
+    b = {"input_ids": ids, "labels": labels, "old_logprobs": old, "ref_logprobs": ref, "advantages": adv, "rewards": rew,
+         "group_tokens": gt, "overflow": ovf, "num_labels": torch.full_like(gt, 43.0)}
+    b = {k: v.cpu().numpy() for k, v in b.items()}
+    cfg_d = dict(policy_loss="ppo", epsilon_low=0.2, epsilon_high=0.2, kl_coef=0.05, final_kl_coef=0.05, batch_size=8, entropy_bonus=0.01,
+                 final_entropy_bonus=0.01)
+    for v, (nlp, ent, grad) in ((0, (n0, e0, g0)), (variant, (n1, e1, g1))):
+        tok = orl.token_loss(b, nlp.cpu().numpy()[:, 1:], ent.cpu().numpy()[:, 1:], cfg_d, 0, 10, False)
+        rid, rg, rgh = gc.token_rows(b["input_ids"], tok["g_nlp"], tok["g_ent"])
+        res = gc.dlogits_error(grad[0].cpu().numpy(), logits[0].cpu().numpy(), rid, rg, rgh, 1.0)
+        print(f"[dlogits] variant {v}: {res.err:.3e} (bound {gc.DLOGITS_BOUND['k1_random_g']:.1e})")
+        assert res.ok(gc.DLOGITS_BOUND["k1_random_g"]), f"variant {v}: {res}"
 
 
 @pytest.mark.parametrize("seed", range(12))

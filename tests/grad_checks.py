@@ -152,7 +152,7 @@ def _witness_block(x, ids, g, gh, temperature):
     coef = g.abs() + gh.abs() * (logp.abs() + H.abs())
     scale = coef * p
     flush = F32_TINY * (1.0 + coef / temperature)
-    rows = torch.arange(x.shape[0])
+    rows = torch.arange(x.shape[0], device=x.device)
     ok = (ids >= 0) & (ids < V)
     want[rows[ok], ids[ok]] += g[ok, 0]
     scale[rows[ok], ids[ok]] += g[ok, 0].abs()
@@ -257,17 +257,31 @@ def token_rows(input_ids, g_nlp_shifted, g_ent_shifted):
 
 
 # ---- the reference's own fp32 arithmetic (the yardstick of every bound) -------------------------------------------------
-def reference_fp32(logits, ids, g_nlp, g_ent, temperature: float, row_block: int = 16):
+def reference_fp32(logits, ids, g_nlp, g_ent, temperature: float, row_block: int = 16, hidden=None, weight=None):
     """torch CPU fp32 restatement of reference rl/__init__.py:207-233 with autograd:
-    returns (d logits [R, V] fp32, new_logprobs [R], entropy [R], logsumexp [R]) for loss = sum(g nlp + gH entropy)."""
-    x, ids = _as_t(logits).float(), _as_t(ids, torch.int64)
+    returns (d logits [R, V] fp32, new_logprobs [R], entropy [R], logsumexp [R]) for loss = sum(g nlp + gH entropy).
+    With `hidden` [R, H] and `weight` [V, H] (`logits` None) the logits are the reference's fp32 head product
+    `hidden.float() @ weight.float().T` (finetune/checkpoints.py:87-103) inside the same graph, and two more values are
+    returned: d hidden [R, H] and d weight [V, H], fp32."""
+    ids = _as_t(ids, torch.int64)
     g, gh = _as_t(g_nlp, torch.float32), _as_t(g_ent, torch.float32)
-    R, V = x.shape
+    head = hidden is not None
+    if head:
+        h = _as_t(hidden).float().requires_grad_(True)
+        w = _as_t(weight).float().requires_grad_(True)
+        R, V = h.shape[0], w.shape[0]
+    else:
+        x = _as_t(logits).float()
+        R, V = x.shape
     grad = np.zeros((R, V), dtype=np.float32)
     nlp, ent, lse = (np.zeros(R, dtype=np.float32) for _ in range(3))
     for a in range(0, R, row_block):
         b = slice(a, min(a + row_block, R))
-        xb = x[b].clone().requires_grad_(True)
+        if head:
+            xb = h[b] @ w.t()
+            xb.retain_grad()
+        else:
+            xb = x[b].clone().requires_grad_(True)
         z = xb / temperature
         sel = torch.gather(z, 1, ids[b].clamp(0, V - 1)[:, None])[:, 0]
         log_norm = torch.logsumexp(z, dim=-1)
@@ -279,6 +293,8 @@ def reference_fp32(logits, ids, g_nlp, g_ent, temperature: float, row_block: int
         (new_lp * g[b] * valid + entropy * gh[b]).sum().backward()
         grad[b] = xb.grad.numpy()
         nlp[b], ent[b], lse[b] = new_lp.detach().numpy(), entropy.detach().numpy(), log_norm.detach().numpy()
+    if head:
+        return grad, nlp, ent, lse, h.grad.numpy(), w.grad.numpy()
     return grad, nlp, ent, lse
 
 

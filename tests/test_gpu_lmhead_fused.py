@@ -18,6 +18,8 @@ import torch
 
 from oracle import rl_loss as orl
 
+import grad_checks as gc
+import head_grad_checks as hg
 from helpers import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -78,7 +80,72 @@ def _run(hidden, W, batch, chunk_rows=None, grad_scale=1.0, keep_logits=None):
     return loss, stats, h.grad, w.grad, head
 
 
-def _compare(loss, stats, gh, gw, want, scale=1.0):
+def _own_logprobs(hidden, W, pb, temperature, skip_unlabelled=True):
+    """Token-aligned (new_logprobs, entropy) [B, L] exactly as `fused_head_loss` forms them: the head's forward on the compact
+    problem of the labelled rows when `skip_unlabelled` applies (the forward is bitwise reproducible, kept logits or not), zeros
+    at the positions nobody reads."""
+    from pipelinerl_amd import fused_head as fh
+
+    B, L, H = hidden.shape
+    head = fh.FusedLmHead(W, backward=False)
+    idx = fh._labelled_rows(pb.labels) if skip_unlabelled else None
+    if idx is None or idx.numel() > (1.0 - fh._MIN_SKIP_FRACTION) * B * L:
+        nlp, ent, _, _ = head.logprob_entropy(hidden, pb.input_ids, temperature)
+        return nlp, ent
+    n = idx.numel()
+    hc = torch.zeros((1, n + 1, H), dtype=torch.bfloat16, device=hidden.device)
+    hc[0, :n] = hidden.reshape(B * L, H).index_select(0, idx)
+    ids = torch.zeros((1, n + 1), dtype=torch.int64, device=hidden.device)
+    ids[0, 1:] = pb.input_ids.reshape(-1).index_select(0, idx + 1)
+    nlp_c, ent_c, _, _ = head.logprob_entropy(hc, ids, temperature)
+    nlp = torch.zeros((B, L), dtype=torch.float32, device=hidden.device)
+    ent = torch.zeros_like(nlp)
+    nlp.view(-1).index_copy_(0, idx + 1, nlp_c[0, 1:])
+    ent.view(-1).index_copy_(0, idx + 1, ent_c[0, 1:])
+    return nlp, ent
+
+
+def _per_entry(hidden, W, input_ids, g_nlp, g_ent, temperature, gh=None, gw=None, scale=1.0, label="", family="randn"):
+    """d hidden / d W entry by entry (tests/head_grad_checks.py) for token-aligned gradients `g_nlp` / `g_ent` [B, L] (numpy;
+    column 0 unused).  A bf16 result is allowed its own rounding; rows without a gradient must be exactly zero."""
+    B, L, H = hidden.shape
+    g_ent = np.zeros_like(g_nlp) if g_ent is None else g_ent
+    rid, g, g_h = gc.token_rows(np.asarray(input_ids), g_nlp[:, 1:] * scale, g_ent[:, 1:] * scale)
+    rnd = lambda t: gc.BF16_ROUNDING if t is not None and t.dtype == torch.bfloat16 else 0.0  # noqa: E731
+    res_h, res_w = hg.head_errors(None if gh is None else gh.reshape(B * L, H), gw, hidden.reshape(B * L, H), W, rid, g, g_h, temperature,
+                                  dh_rounding=rnd(gh), dw_rounding=rnd(gw))
+    for res, product in ((res_h, "d_hidden"), (res_w, "d_weight")):
+        if res is not None:
+            bound = hg.head_bound(family, product, W.dtype)
+            print(f"{label} per entry: {product} {res.err:.3e} (bound {bound:.2e})")
+            assert res.ok(bound), f"{label}: {res}"
+    return res_h, res_w
+
+
+def _per_entry_loss_path(hidden, W, batch, gh, gw, cfg=None, packed=True, scale=1.0, skip_unlabelled=True, label=""):
+    """The per-entry check for gradients that came out of `fused_head_loss`: the token gradients of the witness are the
+    oracle's (`orl.token_loss`) for the kernels' OWN log-probs and entropies, which are themselves held to fp64 here."""
+    from pipelinerl_amd.finetune.types import PipelineBatchEncoding
+
+    cfg = cfg or CFG
+    B, L, H = hidden.shape
+    pb = PipelineBatchEncoding(**{k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in batch.items()}, model_version=0, is_packed=packed).to_device(hidden.device)
+    nlp, ent = _own_logprobs(hidden, W, pb, cfg["temperature"], skip_unlabelled)
+    nlp, ent = nlp.cpu().numpy(), ent.cpu().numpy()
+    res = orl.token_loss(batch, nlp[:, 1:], ent[:, 1:], cfg, 2, 10, packed)
+    g_nlp, g_ent = (np.concatenate([np.zeros((B, 1), dtype=np.float32), res[k]], axis=1) for k in ("g_nlp", "g_ent"))
+    # the log-probs the token gradients were formed from, against fp64, wherever a gradient flows
+    x = hg.logits64(hidden.reshape(B * L, H), W)
+    rid, g, g_h = gc.token_rows(batch["input_ids"], g_nlp[:, 1:], g_ent[:, 1:])
+    w_nlp, w_ent, _ = gc.forward_witness(x, rid, cfg["temperature"], row_block=64)
+    live = np.flatnonzero((g != 0) | (g_h != 0))
+    fwd = max(float(np.abs(nlp.reshape(-1)[live + 1] - w_nlp[live]).max()), float(np.abs(ent.reshape(-1)[live + 1] - w_ent[live]).max()))
+    print(f"{label} forward: {fwd:.3e} nats (bound {hg.HEAD_FWD_BOUND['randn']:.2e})")
+    assert fwd <= hg.HEAD_FWD_BOUND["randn"], (label, fwd)
+    return _per_entry(hidden, W, batch["input_ids"], g_nlp, g_ent, cfg["temperature"], gh, gw, scale, label)
+
+
+def _compare(loss, stats, gh, gw, want, scale=1.0, problem=None, label=""):
     assert abs(loss.item() - float(want["loss"])) <= FP_TOL * abs(float(want["loss"]))
     for k, v in want["stats"].items():
         assert abs(float(stats[k]) - float(v)) <= FP_TOL * max(abs(float(v)), 1.0), k
@@ -86,6 +153,8 @@ def _compare(loss, stats, gh, gw, want, scale=1.0):
     # d hidden is delivered in the hidden states' dtype (bf16): compare before that rounding where possible
     tol_h = FP_TOL if gh.dtype == torch.float32 else 4e-3
     assert rel_err(gh[0].float().cpu().numpy(), want["d_hidden"] * scale) <= tol_h
+    hidden, W, batch = problem
+    _per_entry_loss_path(hidden, W, batch, gh, gw, scale=scale, label=label)
 
 
 @pytest.mark.parametrize("keep", [True, False], ids=["kept_logits", "recompute"])
@@ -99,7 +168,7 @@ def test_small_ragged_shapes(libprl, cuda_device, monkeypatch, tile, T, H, V, ke
     hidden, W, batch, logits64 = _problem(T, H, V, cuda_device, seed=T)
     want = _oracle(hidden, W, batch, logits64)
     loss, stats, gh, gw, _ = _run(hidden, W, batch, keep_logits=keep)
-    _compare(loss, stats, gh, gw, want)
+    _compare(loss, stats, gh, gw, want, problem=(hidden, W, batch), label=f"{T}x{H}x{V} {tile} keep={keep}")
 
 
 @pytest.mark.parametrize("V", [8192, 8200], ids=["whole_tiles", "partial_last_tile"])
@@ -167,7 +236,7 @@ def test_qwen7b_head_shape_vs_oracle(libprl, cuda_device, monkeypatch, tile):
     hidden, W, batch, logits64 = _problem(160, 3584, 152064, cuda_device, seed=3)
     want = _oracle(hidden, W, batch, logits64)
     loss, stats, gh, gw, head = _run(hidden, W, batch, keep_logits=keep)
-    _compare(loss, stats, gh, gw, want)
+    _compare(loss, stats, gh, gw, want, problem=(hidden, W, batch), label=f"qwen7b {tile} keep={keep}")
     # fp32 d hidden straight from the C ABI: the 1e-4 bar without the bf16 rounding of the autograd path
     from pipelinerl_amd.finetune.rl import RLConfig, grpo_loss_from_logprobs, make_loss_config
     from pipelinerl_amd.finetune.types import PipelineBatchEncoding
@@ -178,6 +247,7 @@ def test_qwen7b_head_shape_vs_oracle(libprl, cuda_device, monkeypatch, tile):
     _, _, g_nlp, g_ent = grpo_loss_from_logprobs(c_cfg, pb, nlp, ent)
     gh32 = head.backward_from_token_grads(h, pb.input_ids, CFG["temperature"], lse2, ent, g_nlp, g_ent, None, grad_hidden_dtype=torch.float32)
     assert rel_err(gh32[0].cpu().numpy(), want["d_hidden"]) <= FP_TOL
+    _per_entry(hidden, W, batch["input_ids"], g_nlp.cpu().numpy(), g_ent.cpu().numpy(), CFG["temperature"], gh=gh32, label="qwen7b fp32 d hidden")
 
 
 def test_qwen0p5b_tied_bf16_head_vs_oracle(libprl, cuda_device):
@@ -189,6 +259,8 @@ def test_qwen0p5b_tied_bf16_head_vs_oracle(libprl, cuda_device):
     assert abs(loss.item() - float(want["loss"])) <= FP_TOL * abs(float(want["loss"]))
     assert rel_err(gh[0].float().cpu().numpy(), want["d_hidden"]) <= 4e-3
     assert rel_err(gw.float().cpu().numpy(), want["d_weight"]) <= 4e-3  # delivered in the weight's dtype (bf16)
+    assert gw.dtype == torch.bfloat16 and gh.dtype == torch.bfloat16
+    _per_entry_loss_path(hidden, W, batch, gh, gw, label="qwen0.5b tied bf16")
 
 
 @pytest.mark.parametrize("tile", ["256x256", None], ids=["tile256x256", "default_dispatch"])
@@ -204,7 +276,7 @@ def test_chunked_backward_and_upstream_scale(libprl, cuda_device, monkeypatch, t
     for chunk, scale in ((None, 1.0), (128, 1.0), (100, 0.25), (299, 3.0)):
         for keep in (True, False):
             loss, stats, gh, gw, _ = _run(hidden, W, batch, chunk_rows=chunk, grad_scale=scale, keep_logits=keep)
-            _compare(loss, stats, gh, gw, want, scale)
+            _compare(loss, stats, gh, gw, want, scale, problem=(hidden, W, batch), label=f"chunk={chunk} x{scale} keep={keep}")
 
 
 @pytest.mark.parametrize("tile", ["256x256", "256", "128"], ids=["tile256x256", "tile256x128_ring3", "tile128x128"])
@@ -232,6 +304,7 @@ def test_split_k_hidden_gradient(libprl, cuda_device, monkeypatch, tile, ksplit)
             torch.cuda.synchronize()
             out[ks, dt] = gh[0].float().cpu().numpy()
             assert rel_err(out[ks, dt], want["d_hidden"]) <= (FP_TOL if dt == torch.float32 else 4e-3)
+            _per_entry(hidden, W, batch["input_ids"], g_nlp.cpu().numpy(), g_ent.cpu().numpy(), CFG["temperature"], gh=gh, label=f"ksplit={ks} {dt}")
     # the slices are added in a fixed order: run to run the split result is bitwise stable
     gh = head.backward_from_token_grads(h, pb.input_ids, CFG["temperature"], lse2, ent, g_nlp, g_ent, None, grad_hidden_dtype=torch.float32)
     assert np.array_equal(gh[0].cpu().numpy(), out[ksplit, torch.float32])
@@ -290,6 +363,10 @@ def test_leading_term_hidden_gradient(libprl, cuda_device):
     gh = head.backward_from_token_grads(h, pb.input_ids, CFG["temperature"], lse2, ent, g_nlp, g_ent, None, grad_hidden_dtype=torch.float32)
     err = rel_err(gh[0].cpu().numpy(), want["d_hidden"])
     assert 1e-5 < err <= 6e-3, err  # 2^-9 relative per product, not the 1e-4 of the three-term default
+    rid, g, g_h = gc.token_rows(batch["input_ids"], g_nlp.cpu().numpy()[:, 1:], g_ent.cpu().numpy()[:, 1:])
+    res, _ = hg.head_errors(gh[0], None, hidden[0], W, rid, g, g_h, CFG["temperature"])
+    print(f"hidden_grad_terms=1 per entry: {res.err:.3e}")
+    assert hg.head_bound("randn", "d_hidden", W.dtype, 3) < res.err and res.ok(hg.head_bound("randn", "d_hidden", W.dtype, 1)), str(res)
 
 
 def test_rl_step_fused_head_on_a_huggingface_style_model(libprl, cuda_device):
@@ -394,6 +471,7 @@ def test_other_loss_configurations_vs_oracle(libprl, cuda_device, cfg_name, cfg)
         assert abs(float(stats[k]) - float(v)) <= FP_TOL * max(abs(float(v)), 1.0), k
     assert rel_err(w.grad.cpu().numpy(), (dl.t() @ hidden[0].double()).cpu().numpy()) <= FP_TOL
     assert rel_err(h.grad[0].float().cpu().numpy(), (dl @ W.double()).cpu().numpy()) <= 4e-3  # delivered in bf16
+    _per_entry_loss_path(hidden, W, batch, h.grad, w.grad, cfg=cfg, label=cfg_name)
     if cfg_name == "grpo_no_kl_no_entropy":
         assert torch.count_nonzero(h.grad[0, 39:59]) == 0
 
@@ -429,6 +507,8 @@ def test_unlabelled_rows_are_skipped_without_changing_the_result(libprl, cuda_de
         loss, stats = fused_head_loss(h, w, head, pb, RLConfig(**CFG), 2, 10)
         loss.backward()
         out[skip] = (loss.item(), stats, h.grad.float().cpu().numpy(), w.grad.cpu().numpy())
+        # the compact path (and the full one) per entry; rows without a label must be exactly zero in d hidden
+        _per_entry_loss_path(hidden, W, batch, h.grad, w.grad, packed=packed, skip_unlabelled=skip, label=f"{layout} skip_unlabelled={skip}")
         assert abs(loss.item() - float(want["loss"])) <= FP_TOL * abs(float(want["loss"]))
         for k, v in want["stats"].items():
             assert abs(float(stats[k]) - float(v)) <= FP_TOL * max(abs(float(v)), 1.0), (skip, k)

@@ -46,6 +46,8 @@
  *   prl_bucket_*                  pipelinerl/finetune_loop.py:205-292,
  *                                 pipelinerl/vllm1.py:62-134,
  *                                 pipelinerl/torch_utils.py:70-94
+ *   prl_optim_*                   pipelinerl/finetune/optim.py:25-112 (AdamW / Lion) and the
+ *                                 clip_grad_norm_ + optimizer.step() of pipelinerl/finetune_loop.py:738-744
  */
 #ifndef PRL_H_
 #define PRL_H_
@@ -57,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PRL_ABI_VERSION 13
+#define PRL_ABI_VERSION 14
 
 #define PRL_OK 0
 #define PRL_EINVAL (-22)   /* bad argument                                  */
@@ -607,6 +609,45 @@ struct prl_segment {
 };
 int prl_bucket_gather(void* bucket, int64_t bucket_bytes, const struct prl_segment* segments, int64_t n_segments, void* stream);
 int prl_bucket_scatter(const void* bucket, int64_t bucket_bytes, const struct prl_segment* segments, int64_t n_segments, void* stream);
+
+/* ---- learner-step boundary: gradient norm + clip coefficient, fused AdamW / Lion step -----------------------
+ * Replaces `torch.nn.utils.clip_grad_norm_` -> `float(gn)` -> `optimizer.step()` of finetune_loop.py:738-744
+ * and the optimizers finetune/optim.py:25-112 builds, as multi-tensor launches: one read pass over all
+ * gradients, then ONE read-modify-write pass per parameter that applies the clip coefficient from device
+ * memory (gradients are not rewritten), updates the fp32 state and writes the parameter in its own dtype at
+ * its own address (bf16: round to nearest even).  The per-element operations are those of torch.optim.AdamW
+ * (single-tensor path, amsgrad off, decoupled decay) and of the reference's Lion.step, in their order; the
+ * fp32 constants are formed from the doubles below the way Python forms them.
+ *   `segments` is a HOST array; every pointer in it is a device pointer.  A segment with `grad == NULL` or
+ *   `numel == 0` is skipped.  `master == NULL`: the parameter itself is read and updated in its dtype;
+ *   otherwise `master` holds the fp32 weights of a bf16 parameter, which is only written.  `exp_avg`,
+ *   `exp_avg_sq` (AdamW only) are fp32.  `step` is the number of THIS update (1 for the first).
+ *   Nothing allocates or synchronises; arguments are validated before any device work (PRL_EINVAL names the
+ *   segment).  Pointers that are not 16-byte aligned take a scalar path.
+ * prl_optim_grad_norm writes norm_and_coef[0] = L2 norm over every segment with a gradient (fp64 sums in a
+ *   fixed order: bitwise reproducible) and norm_and_coef[1] = min(1, max_norm / (norm + 1e-6)) formed in fp32
+ *   as clip_grad_norm_ does (a non-finite norm propagates); max_norm <= 0 gives 1.
+ * The step calls read the coefficient from `norm_and_coef` (NULL = 1). */
+typedef struct prl_optim_segment {
+  void* param;
+  const void* grad;
+  void* master;
+  void* exp_avg;
+  void* exp_avg_sq;
+  int64_t numel;
+  int64_t step;
+  int32_t param_dtype; /* PRL_DTYPE_* */
+  int32_t grad_dtype;  /* PRL_DTYPE_* */
+  double lr;
+  double weight_decay;
+} prl_optim_segment;
+int prl_optim_workspace_bytes(int64_t n_segments, int64_t total_numel, size_t* bytes);
+int prl_optim_grad_norm(const prl_optim_segment* segments, int64_t n_segments, float max_norm, void* workspace,
+                        size_t workspace_bytes, float* norm_and_coef, prl_stream_t stream);
+int prl_optim_adamw_step(const prl_optim_segment* segments, int64_t n_segments, double beta1, double beta2, double eps,
+                         const float* norm_and_coef, prl_stream_t stream);
+int prl_optim_lion_step(const prl_optim_segment* segments, int64_t n_segments, double beta1, double beta2,
+                        const float* norm_and_coef, prl_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
 /* Fused output head: hidden states -> new_logprobs / entropy, logits never   */

@@ -13,7 +13,7 @@ from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libprl.so"
 
-PRL_ABI_VERSION = 13
+PRL_ABI_VERSION = 14
 PRL_OK = 0
 PRL_EINVAL = -22
 PRL_ENOMEM = -12
@@ -126,6 +126,14 @@ class PrlSegment(ctypes.Structure):
     _fields_ = [("tensor", c_void_p), ("bucket_offset", c_int64), ("nbytes", c_int64)]
 
 
+class PrlOptimSegment(ctypes.Structure):
+    """Mirror of `struct prl_optim_segment` (include/prl.h)."""
+
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("master", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("numel", c_int64), ("step", c_int64), ("param_dtype", c_int32), ("grad_dtype", c_int32),
+                ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double)]
+
+
 class PrlError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libprl error {code}: {message}")
@@ -199,6 +207,10 @@ PROTOTYPES: dict[str, tuple] = {
     "prl_ipc_close": (c_int32, [c_void_p]),
     "prl_bucket_gather": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "prl_bucket_scatter": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "prl_optim_workspace_bytes": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
+    "prl_optim_grad_norm": (c_int32, [_P, c_int64, c_float, _P, c_size_t, _P, _P]),
+    "prl_optim_adamw_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "prl_optim_lion_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, _P, _P]),
     "prl_lm_head_prepare": (c_int32, [c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, _P]),
     "prl_lm_head_workspace_bytes": (c_int32, [c_int64, c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t), POINTER(c_size_t)]),
     "prl_lm_head_logprob_fwd": (c_int32, [c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_size_t, _P]),

@@ -683,10 +683,15 @@ class LearnerStep:
         m.samples = self.start_samples + self.total_samples
         m.tokens += sum(self._tokens) * self.world
         assert sum(self._micro_batch_sizes) == self.samples_per_lead_per_step
-        if self.gradient_clipping_threshold is not None:
-            gn = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold)
-            m.grad_norm = float(gn)
-        self.optimizer.step()
+        if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
+            # fused boundary (finetune/optim.py): norm pass + step, the clip coefficient stays on the device; the norm is read
+            # once both are enqueued
+            m.grad_norm = float(self.optimizer.clip_and_step(self.gradient_clipping_threshold))
+        else:
+            if self.gradient_clipping_threshold is not None:
+                gn = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold)
+                m.grad_norm = float(gn)
+            self.optimizer.step()
         self.optimizer.zero_grad()
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()
@@ -804,8 +809,20 @@ class StreamedLearnerStep(LearnerStep):
 
         # ---- accumulation boundary: the step's statistics in ONE copy, then the optimizer step (:810-857)
         _, kl_coef, ent_coef = make_loss_config(self.rl_config, m.completed_steps, self.max_train_steps)
+        # fused boundary (finetune/optim.py): the norm pass runs first and its result rides in the ONE statistics copy below
+        gn_dev = None
+        if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
+            gn_dev = self.optimizer.compute_grad_norm(self.gradient_clipping_threshold)
+            if not self._stats_dev:
+                grad_norm = float(gn_dev)
         if self._stats_dev:
-            rows = torch.stack(self._stats_dev).cpu().tolist()
+            if gn_dev is None:
+                rows = torch.stack(self._stats_dev).cpu().tolist()
+            else:
+                block = torch.stack(self._stats_dev)
+                flat = torch.cat([block.flatten(), gn_dev.to(block.dtype).reshape(1)]).cpu().tolist()
+                grad_norm = flat.pop()
+                rows = [flat[i * block.shape[1]:(i + 1) * block.shape[1]] for i in range(block.shape[0])]
             for row, size in zip(rows, self._input_sizes):
                 vstats = row[_lib.PRL_NUM_STATS:]
                 if vstats:
@@ -827,10 +844,14 @@ class StreamedLearnerStep(LearnerStep):
         m.samples = self.start_samples + self.total_samples
         m.tokens += sum(self._tokens) * self.world
         assert sum(self._micro_batch_sizes) == self.samples_per_lead_per_step
-        if self.gradient_clipping_threshold is not None:
-            gn = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold)
-            m.grad_norm = float(gn)
-        self.optimizer.step()
+        if gn_dev is not None:
+            m.grad_norm = grad_norm
+            self.optimizer.step(clipped=True)  # the coefficient of the norm pass above, read on the device
+        else:
+            if self.gradient_clipping_threshold is not None:
+                gn = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold)
+                m.grad_norm = float(gn)
+            self.optimizer.step()
         self.optimizer.zero_grad()
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()
@@ -1010,9 +1031,13 @@ class NativeLearnerStep:
         if self.has_value_head:
             value_stats = self._reduce_value_stats(vacc if vacc is not None else torch.zeros(5, dtype=torch.float64, device=rollouts.device))
             loss = loss + self.rl_config.value_loss_coef * value_stats[3].to(loss.dtype)
-        if self.gradient_clipping_threshold is not None:
-            self.metrics.grad_norm = float(torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold))
-        self.optimizer.step()
+        if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
+            # fused boundary (finetune/optim.py): nothing waits between the norm and the step; the norm is read once both are enqueued
+            self.metrics.grad_norm = float(self.optimizer.clip_and_step(self.gradient_clipping_threshold))
+        else:
+            if self.gradient_clipping_threshold is not None:
+                self.metrics.grad_norm = float(torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold))
+            self.optimizer.step()
         self.optimizer.zero_grad()
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()

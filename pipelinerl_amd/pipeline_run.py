@@ -76,7 +76,7 @@ class PipelineSpec:
     engine_load: bool = False          # the engine runs forward passes between updates (a colocated actor's GPU share)
     gradient_checkpointing: bool = False
     learner: str = "streamed"          # "streamed" (StreamedLearnerStep) or "dropin" (LearnerStep + rl_step_fused_head)
-    optimizer: str = "adamw"           # "adamw" | "sgd" (parity tests)
+    optimizer: str = "adamw"           # "adamw" | "adamw_hip" (finetune/optim.py FusedAdamW) | "sgd" (parity tests)
     param_dtype: str = "bf16"          # "bf16" (the reference's training dtype) | "fp32" (parity tests: tight parameter deltas)
     kl_coef: float = 0.0               # > 0 (configs[4]: 0.001): KL-to-reference on - the preprocessor holds the frozen reference policy (the initial policy) and writes `ref_logprobs`
     ref_seed: int | None = None        # seed of the reference policy (default: `seed`, i.e. the policy the run starts from)
@@ -593,6 +593,10 @@ def learner_stage(spec: PipelineSpec, rank: int = 0, name: str = "learner") -> N
         train_model = torch.nn.parallel.DistributedDataParallel(model, **({"device_ids": [dev.index]} if cuda and spec.learner_backend == "nccl" else {}))
     if spec.optimizer == "sgd":
         opt = torch.optim.SGD(train_model.parameters(), lr=spec.lr)
+    elif spec.optimizer == "adamw_hip":
+        from .finetune.optim import FusedAdamW
+
+        opt = FusedAdamW(train_model.parameters(), lr=spec.lr)
     else:
         opt = torch.optim.AdamW(train_model.parameters(), lr=spec.lr, fused=cuda)
     rl = rl_config_of(spec)

@@ -1,0 +1,132 @@
+"""Time the learner-step boundary on the Qwen2.5-7B parameter list (`weight_sync_probe.qwen25_shapes("7b")`): bf16 parameters
+and gradients, the output head in fp32.
+
+  torch            clip_grad_norm_ + float() + torch.optim.AdamW(fused=True).step()   (bf16 state; the boundary before FusedAdamW)
+  fused            FusedAdamW.clip_and_step, master weights off                        (fp32 state, like for like in what is updated)
+  fused_master     FusedAdamW.clip_and_step, master weights on                         (moves more bytes: + 8 B per bf16 element)
+
+HIP events around every boundary, >= 20 timed boundaries after warm-up.  Every configuration runs in a child process of its
+own under its own time limit; the first one that fails ends the run.  One JSON object on stdout and in --out.
+
+    python scripts/optim_step_bench.py --out profiles/optim_step_bench.json
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import subprocess
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+PEAK_GBS, COPY_CEILING_GBS = 8000.0, 6290.0
+CONFIGS = ("torch", "fused", "fused_master")
+
+
+def bytes_needed(shapes, config: str) -> int:
+    total = 0
+    for name, shape in shapes:
+        n = 1
+        for d in shape:
+            n *= d
+        e = 4 if name == "lm_head.weight" else 2
+        state = {"torch": 2 * e, "fused": 8, "fused_master": 8 + (4 if e == 2 else 0)}[config]
+        total += n * (2 * e + state)
+    return total
+
+
+def run_one(config: str, steps: int, warmup: int, max_norm: float) -> dict:
+    import torch
+
+    from pipelinerl_amd.finetune.optim import FusedAdamW
+    from pipelinerl_amd.weight_sync_probe import qwen25_shapes
+
+    dev = torch.device("cuda", 0)
+    shapes = qwen25_shapes("7b")
+    free, _ = torch.cuda.mem_get_info(dev)
+    full = len(shapes)
+    while bytes_needed(shapes, config) > 0.9 * free:  # the largest prefix of the list that fits
+        shapes = shapes[:-1]
+    params = []
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for name, shape in shapes:
+        dtype = torch.float32 if name == "lm_head.weight" else torch.bfloat16
+        p = torch.nn.Parameter(torch.empty(shape, dtype=dtype, device=dev).normal_(0.0, 0.02, generator=gen))
+        p.grad = torch.empty(shape, dtype=dtype, device=dev).normal_(0.0, 1e-3, generator=gen)
+        params.append(p)
+    numel = sum(p.numel() for p in params)
+    if config == "torch":
+        opt = torch.optim.AdamW(params, lr=1e-6, fused=True)
+
+        def boundary():
+            gn = torch.nn.utils.clip_grad_norm_(params, max_norm)
+            float(gn)
+            opt.step()
+    else:
+        opt = FusedAdamW(params, lr=1e-6, master_weights=config == "fused_master")
+
+        def boundary():
+            opt.clip_and_step(max_norm)
+
+    times = []
+    for k in range(warmup + steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        boundary()
+        b.record()
+        b.synchronize()
+        if k >= warmup:
+            times.append(a.elapsed_time(b))
+    out = {"config": config, "tensors": len(params), "of_tensors": full, "numel": numel, "steps": steps, "warmup": warmup,
+           "median_ms": statistics.median(times), "min_ms": min(times), "max_ms": max(times)}
+    if config != "torch":
+        # algorithmic bytes: the norm pass reads every gradient once; the step reads g, weights, m, v and writes weights (+ the bf16
+        # image under master weights), m, v
+        alg = 0
+        for p in params:
+            e = p.element_size()
+            master = config == "fused_master" and e == 2
+            alg += p.numel() * (e + e + (4 if master else e) + 8 + (4 if master else 0) + e + 8)
+        gbs = alg / (out["median_ms"] * 1e-3) / 1e9
+        out.update(algorithmic_bytes=alg, achieved_gbs=gbs, frac_of_peak=gbs / PEAK_GBS, frac_of_copy_ceiling=gbs / COPY_CEILING_GBS)
+    return out
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--max-norm", type=float, default=0.3)
+    ap.add_argument("--timeout", type=int, default=300, help="seconds per configuration")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--one", choices=CONFIGS, default=None, help="(child) run one configuration in this process")
+    args = ap.parse_args()
+    if args.one:
+        print("RESULT " + json.dumps(run_one(args.one, args.steps, args.warmup, args.max_norm)), flush=True)
+        return
+    results = {}
+    for config in CONFIGS:
+        cmd = [sys.executable, __file__, "--one", config, "--steps", str(args.steps), "--warmup", str(args.warmup), "--max-norm", str(args.max_norm)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
+        line = next((l for l in res.stdout.splitlines() if l.startswith("RESULT ")), None)
+        if res.returncode != 0 or line is None:
+            raise SystemExit(f"{config}: exit status {res.returncode}\n{res.stdout[-2000:]}\n{res.stderr[-4000:]}")
+        results[config] = json.loads(line[len("RESULT "):])
+    a, b = results["torch"], results["fused"]
+    report = {"workload": "Qwen2.5-7B parameter list, bf16 parameters and gradients, fp32 lm_head, AdamW, clip at %g" % args.max_norm,
+              "results": results, "spread_torch_ms": a["max_ms"] - a["min_ms"],
+              "like_for_like_gain_ms": a["median_ms"] - b["median_ms"],
+              "fused_is_faster_by_more_than_the_spread": (a["median_ms"] - b["median_ms"]) > (a["max_ms"] - a["min_ms"])}
+    text = json.dumps(report, indent=1)
+    print(text)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

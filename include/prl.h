@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PRL_ABI_VERSION 14
+#define PRL_ABI_VERSION 15
 
 #define PRL_OK 0
 #define PRL_EINVAL (-22)   /* bad argument                                  */
@@ -648,6 +648,24 @@ int prl_optim_adamw_step(const prl_optim_segment* segments, int64_t n_segments, 
                          const float* norm_and_coef, prl_stream_t stream);
 int prl_optim_lion_step(const prl_optim_segment* segments, int64_t n_segments, double beta1, double beta2,
                         const float* norm_and_coef, prl_stream_t stream);
+
+/* Gradient accumulation in fp32: folds ONE micro-batch's gradients into the accumulators the calls above then
+ * read as `grad` (grad_dtype PRL_DTYPE_F32).  Autograd sums micro-batch gradients in the parameter's dtype; a
+ * bf16 running sum drops every term below half an ulp of it (1024 passes: finetune/base.yaml:45).
+ *   overwrite != 0: acc[i] = (float)grad[i]           first fold of a step; acc is not read (no zeroing pass)
+ *   overwrite == 0: acc[i] = acc[i] + (float)grad[i]  one IEEE fp32 add, no scaling: defined bit for bit
+ * `segments` is a HOST array of device pointers; `grad == NULL` or `numel == 0` is skipped; multi-tensor
+ * launches of <= 64 segments, no atomics, nothing allocates or synchronises; arguments are validated before
+ * any device work (PRL_EINVAL names the segment).  Pointers that are not 16-byte aligned take a scalar path. */
+typedef struct prl_accum_segment {
+  const void* grad;   /* this micro-batch's gradient, PRL_DTYPE_BF16 or PRL_DTYPE_F32 */
+  void* acc;          /* fp32 accumulator, numel elements */
+  int64_t numel;
+  int32_t grad_dtype;
+  int32_t reserved;   /* 0 */
+} prl_accum_segment;
+int prl_optim_grad_accumulate(const prl_accum_segment* segments, int64_t n_segments,
+                              int32_t overwrite, prl_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
 /* Fused output head: hidden states -> new_logprobs / entropy, logits never   */

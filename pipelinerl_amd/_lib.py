@@ -13,7 +13,7 @@ from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libprl.so"
 
-PRL_ABI_VERSION = 14
+PRL_ABI_VERSION = 15
 PRL_OK = 0
 PRL_EINVAL = -22
 PRL_ENOMEM = -12
@@ -126,6 +126,12 @@ class PrlSegment(ctypes.Structure):
     _fields_ = [("tensor", c_void_p), ("bucket_offset", c_int64), ("nbytes", c_int64)]
 
 
+class PrlAccumSegment(ctypes.Structure):
+    """Mirror of `struct prl_accum_segment` (include/prl.h)."""
+
+    _fields_ = [("grad", c_void_p), ("acc", c_void_p), ("numel", c_int64), ("grad_dtype", c_int32), ("reserved", c_int32)]
+
+
 class PrlOptimSegment(ctypes.Structure):
     """Mirror of `struct prl_optim_segment` (include/prl.h)."""
 
@@ -211,6 +217,7 @@ PROTOTYPES: dict[str, tuple] = {
     "prl_optim_grad_norm": (c_int32, [_P, c_int64, c_float, _P, c_size_t, _P, _P]),
     "prl_optim_adamw_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
     "prl_optim_lion_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "prl_optim_grad_accumulate": (c_int32, [_P, c_int64, c_int32, _P]),
     "prl_lm_head_prepare": (c_int32, [c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, _P]),
     "prl_lm_head_workspace_bytes": (c_int32, [c_int64, c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t), POINTER(c_size_t)]),
     "prl_lm_head_logprob_fwd": (c_int32, [c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_size_t, _P]),

@@ -1,5 +1,6 @@
 // Learner-step boundary: gradient norm + clip coefficient, then the AdamW / Lion update of EVERY parameter,
-// as multi-tensor launches (one per <= 64 gradients for the norm, per <= 32 parameters for the step).
+// as multi-tensor launches (one per <= 64 gradients for the norm, per <= 32 parameters for the step); and, in front of it, the
+// fold of every micro-batch's gradients into fp32 accumulators (one launch per <= 64 gradients).
 //
 // Replaces `torch.nn.utils.clip_grad_norm_` -> `float(gn)` -> `optimizer.step()` of
 // pipelinerl/finetune_loop.py:738-744 (a multi-pass foreach norm, a host sync, an in-place rescale of every
@@ -25,6 +26,7 @@ constexpr int kBlock = 256;
 constexpr int kGroup = 8;                  // elements per lane and iteration
 constexpr int64_t kChunk = 16 << 10;       // elements per workgroup: 8 iterations of 256 lanes x 8 elements
 constexpr int kNormSegs = 64;              // per launch: 64 x 21 B of kernel arguments
+constexpr int kAccumSegs = 64;             // per launch: 64 x 29 B
 constexpr int kStepSegs = 32;              // per launch: 32 x 90 B (64 would not fit 4 KB of kernel arguments)
 constexpr int kFinalBlock = 1024;
 
@@ -275,6 +277,53 @@ __global__ __launch_bounds__(kBlock) void optim_step_kernel(const StepTable<Rule
   }
 }
 
+// ---- gradient accumulation ---------------------------------------------------------------------------------------------
+// acc (fp32) = [acc +] (float)grad, one micro-batch.  10 B/element for a bf16 gradient (2 + 4 read, 4 written), 6 on the overwriting
+// first fold of a step (the accumulator is not read: no zeroing pass exists), 12 / 8 for an fp32 gradient.  Every element is owned by
+// one lane: no atomics, and the sum over the micro-batches is the sequential fp32 sum in fold order.
+struct AccumTable {
+  const void* grad[kAccumSegs];
+  float* acc[kAccumSegs];
+  int64_t numel[kAccumSegs];
+  int32_t first_chunk[kAccumSegs + 1];
+  uint8_t bf16[kAccumSegs];
+  int32_t n;
+};
+
+template <bool GB, bool OVERWRITE>
+__device__ __forceinline__ void chunk_accumulate(const void* grad, float* acc, int64_t len) {
+  int64_t done = 0;
+  if (aligned16_dev(grad) && aligned16_dev(acc)) {
+    const int64_t ngroups = len / kGroup;
+    for (int64_t q = threadIdx.x; q < ngroups; q += kBlock) {
+      const int64_t i = q * kGroup;
+      float g[kGroup], a[kGroup];
+      load8<GB>(grad, i, g);
+      if constexpr (!OVERWRITE) load8<false>(acc, i, a);
+#pragma unroll
+      for (int k = 0; k < kGroup; ++k) a[k] = OVERWRITE ? prl_grad_accum_first(g[k]) : prl_grad_accum_add(a[k], g[k]);
+      store8_stream(acc, i, a);  // read next by the following fold, a whole backward later
+    }
+    done = ngroups * kGroup;
+  }
+  for (int64_t i = done + threadIdx.x; i < len; i += kBlock) {  // tail, or a whole unaligned view
+    const float g = load1<GB>(grad, i);
+    acc[i] = OVERWRITE ? prl_grad_accum_first(g) : prl_grad_accum_add(acc[i], g);
+  }
+}
+
+template <bool OVERWRITE>
+__global__ __launch_bounds__(kBlock) void grad_accumulate_kernel(const AccumTable tab) {
+  const int chunk = blockIdx.x;
+  const int s = owner(tab.first_chunk, tab.n, chunk);
+  const int64_t begin = int64_t(chunk - tab.first_chunk[s]) * kChunk;
+  const int64_t left = tab.numel[s] - begin;
+  const int64_t len = left < kChunk ? left : kChunk;
+  float* acc = tab.acc[s] + begin;
+  if (tab.bf16[s]) chunk_accumulate<true, OVERWRITE>(static_cast<const uint16_t*>(tab.grad[s]) + begin, acc, len);
+  else chunk_accumulate<false, OVERWRITE>(static_cast<const float*>(tab.grad[s]) + begin, acc, len);
+}
+
 int64_t chunks_of(int64_t numel) { return (numel + kChunk - 1) / kChunk; }
 bool live(const prl_optim_segment& s) { return s.grad != nullptr && s.numel > 0; }
 
@@ -396,4 +445,41 @@ extern "C" int prl_optim_lion_step(const prl_optim_segment* segments, int64_t n_
   if (int rc = validate(segments, n_segments, true, false)) return rc;
   PRL_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "betas (%g, %g) outside [0, 1)", beta1, beta2);
   return step_launches<LionRule>(segments, n_segments, beta1, beta2, 0.0, norm_and_coef, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int prl_optim_grad_accumulate(const prl_accum_segment* segments, int64_t n_segments, int32_t overwrite, prl_stream_t stream) {
+  PRL_CHECK_ARG(n_segments >= 0, "negative segment count");
+  PRL_CHECK_ARG(n_segments == 0 || segments != nullptr, "null segment table with %lld segments", (long long)n_segments);
+  for (int64_t i = 0; i < n_segments; ++i) {
+    const prl_accum_segment& s = segments[i];
+    PRL_CHECK_ARG(s.numel >= 0, "segment %lld: negative numel %lld", (long long)i, (long long)s.numel);
+    PRL_CHECK_ARG(chunks_of(s.numel) < (int64_t(1) << 30), "segment %lld: %lld elements are too many for one launch", (long long)i, (long long)s.numel);
+    PRL_CHECK_ARG(s.grad_dtype == PRL_DTYPE_F32 || s.grad_dtype == PRL_DTYPE_BF16, "segment %lld: unknown grad_dtype %d", (long long)i, s.grad_dtype);
+    PRL_CHECK_ARG(s.grad == nullptr || s.numel == 0 || s.acc != nullptr, "segment %lld: null acc", (long long)i);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int64_t i = 0;
+  while (i < n_segments) {
+    AccumTable tab;
+    tab.n = 0;
+    tab.first_chunk[0] = 0;
+    int64_t chunks = 0;
+    for (; i < n_segments && tab.n < kAccumSegs; ++i) {
+      const prl_accum_segment& s = segments[i];
+      if (s.grad == nullptr || s.numel == 0) continue;
+      const int64_t c = chunks_of(s.numel);
+      if (chunks + c > (int64_t(1) << 30)) break;  // keep the grid and the prefix sums in int32
+      tab.grad[tab.n] = s.grad;
+      tab.acc[tab.n] = static_cast<float*>(s.acc);
+      tab.numel[tab.n] = s.numel;
+      tab.bf16[tab.n] = s.grad_dtype == PRL_DTYPE_BF16;
+      chunks += c;
+      tab.first_chunk[++tab.n] = int32_t(chunks);
+    }
+    if (tab.n == 0) break;  // only skipped segments were left
+    if (overwrite) hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3(unsigned(chunks)), dim3(kBlock), 0, st, tab);
+    else hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3(unsigned(chunks)), dim3(kBlock), 0, st, tab);
+    PRL_LAUNCH_CHECK("grad_accumulate_kernel");
+  }
+  return PRL_OK;
 }

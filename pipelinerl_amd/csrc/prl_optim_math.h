@@ -21,6 +21,10 @@
 //
 // The gradient is multiplied by the clip coefficient on the way in (what clip_grad_norm_'s
 // `g.mul_(clip_coef)` leaves behind, without writing it back).
+//
+// Gradient accumulation (grad_accumulate_kernel): the micro-batch gradient is widened to fp32 (exact for bf16)
+// and added to the fp32 accumulator with ONE IEEE add, no scaling: `acc + g.float()` of torch, bit for bit.
+// The first fold of a step stores the widened gradient and never reads the accumulator.
 #pragma once
 
 #include <math.h>
@@ -127,3 +131,7 @@ PRL_OPT_HD void prl_lion_update(const PrlLionScalars& s, float coef, float g, fl
   p = (update != update) ? update : __builtin_fmaf(sgn, s.neg_lr, p);  // ... and torch.sign(NaN) is NaN
   m = __builtin_fmaf(g, s.omb2, m * s.beta2);
 }
+
+// One micro-batch gradient folded into the fp32 accumulator: the first fold of a step / every later one.
+PRL_OPT_HD float prl_grad_accum_first(float g) { return g; }
+PRL_OPT_HD float prl_grad_accum_add(float acc, float g) { return acc + g; }

@@ -20,6 +20,16 @@ parameter's storage (`ColocatedSender.rehome`) is fine: the values travel, and t
 Data parallelism: gradients are already reduced when the accumulation boundary is reached (DDP averages them in backward), so
 the norm computed here is complete on every rank.  ZeRO / FSDP sharded norms are out of scope.
 
+Gradient accumulation (`grad_accum_dtype=torch.float32`): autograd sums the micro-batch gradients into `p.grad` in the
+parameter's dtype, and a bf16 running sum drops every term below half an ulp of it - after 256 equal terms all of the next one.
+The reference accumulates in fp32 (FSDP `param_dtype / reduce_dtype: fp32`, DeepSpeed's fp32 gradient partitions).  With the
+option, `accumulate_grads()` after every `backward()` folds each bf16 `p.grad` into an fp32 accumulator (one IEEE add per
+element and micro-batch, `prl_optim_grad_accumulate`) and clears `p.grad`; norm and step read the accumulators;
+`reduce_accumulated(group)` averages them over the data-parallel ranks in fp32 (run every pass under `no_sync()`: DDP would
+reduce the last micro-batch's `p.grad` only).  fp32 gradients (the fp32 `lm_head`, which the fused head already accumulates
+into in fp32) are used as they are.  The accumulators are views of one flat buffer, transient (not in `state_dict()`), and
+cost 4 bytes per bf16 element: 28 GB on the Qwen2.5-7B list.
+
 There is no CPU path: parameters that are not on a HIP device raise.
 """
 
@@ -64,9 +74,16 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     _state_keys: tuple[str, ...] = ("exp_avg",)
 
-    def __init__(self, params: Iterable, defaults: dict[str, Any], master_weights: bool):
+    def __init__(self, params: Iterable, defaults: dict[str, Any], master_weights: bool, grad_accum_dtype: torch.dtype | None = None):
+        if grad_accum_dtype not in (None, torch.float32):
+            raise ValueError(f"fused optimizer: grad_accum_dtype must be None or torch.float32 (got {grad_accum_dtype})")
         super().__init__(params, defaults)
         self.master_weights = bool(master_weights)
+        self.grad_accum_dtype = grad_accum_dtype
+        self._acc_flat: torch.Tensor | None = None      # the flat fp32 accumulator buffer (slot-padded like the state)
+        self._acc: dict[torch.Tensor, torch.Tensor] = {}  # parameter -> its view of the buffer
+        self._acc_filled: set[torch.Tensor] = set()     # folded at least once since the last step / zero_grad
+        self._acc_zeroed: dict[torch.Tensor, tuple[torch.Tensor, int]] = {}  # accumulate_grads(set_to_none=False): the zeroed p.grad and its version
         self._flat: list[torch.Tensor] = []       # the flat state buffers (kept alive here; state entries are views)
         self._table = None                        # ctypes array of PrlOptimSegment, one per parameter
         self._table_key: list[tuple[int, int]] = []
@@ -89,7 +106,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         for group in self.param_groups:
             todo = []
             for p in group["params"]:
-                if p.grad is None:
+                if self._grad_of(p) is None:
                     continue
                 st = self.state[p]
                 keys = self._keys_of(p)
@@ -142,6 +159,126 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 self.state[p]["step"] = torch.as_tensor(src["step"], dtype=torch.float32).detach().cpu().clone()
         self._flat, self._table, self._table_key = [], None, []
 
+    # ---- fp32 gradient accumulation ---------------------------------------------------------------------------------------
+    def _grad_of(self, p: torch.Tensor) -> torch.Tensor | None:
+        """What norm and step read for `p`: its accumulator once something was folded into it, else `p.grad`."""
+        if p in self._acc_filled:
+            return self._acc[p]
+        return p.grad
+
+    @staticmethod
+    def _accumulates(p: torch.Tensor) -> bool:
+        """The static rule (the same on every rank): a parameter whose gradient dtype is not fp32 has an accumulator."""
+        return (getattr(p, "grad_dtype", None) or p.dtype) != torch.float32
+
+    def _unfolded(self, p: torch.Tensor) -> bool:
+        g = p.grad
+        if g is None or g.dtype == torch.float32:
+            return False
+        z = self._acc_zeroed.get(p)
+        return not (z is not None and z[0] is g and z[1] == g._version)  # zeroed in place by the last fold and untouched since
+
+    def _check_all_folded(self) -> None:
+        if self.grad_accum_dtype is None:
+            return
+        left = sum(self._unfolded(p) for group in self.param_groups for p in group["params"])
+        if left:
+            raise RuntimeError(f"fused optimizer: {left} parameter(s) hold a micro-batch gradient that was not folded into the fp32 accumulators; "
+                               "call accumulate_grads() after every backward()")
+
+    def _ensure_accumulators(self, extra: Iterable[torch.Tensor] = ()) -> None:
+        """One flat fp32 buffer with a 64-byte aligned slot per accumulating parameter; rebuilt (filled slots copied) when a parameter joins."""
+        owners = [p for group in self.param_groups for p in group["params"] if self._accumulates(p) or p in self._acc]
+        have = {id(p) for p in owners}
+        owners += [p for p in extra if id(p) not in have]
+        if self._acc_flat is not None and len(owners) == len(self._acc) and all(p in self._acc for p in owners):
+            return
+        if not owners:
+            return
+        devices = {p.device for p in owners}
+        if len(devices) > 1:
+            raise ValueError(f"fused optimizer: all parameters must live on one device (got {sorted(map(str, devices))})")
+        slots = [(-(-p.numel() // _SLOT)) * _SLOT for p in owners]
+        flat = torch.zeros(sum(slots), dtype=torch.float32, device=owners[0].device)  # zeros: the padding takes part in the all-reduce
+        views, off = {}, 0
+        for p, slot in zip(owners, slots):
+            views[p] = flat[off:off + p.numel()].view(p.shape)
+            off += slot
+            if p in self._acc_filled:
+                views[p].copy_(self._acc[p])
+        self._acc_flat, self._acc = flat, views
+
+    @torch.no_grad()
+    def accumulate_grads(self, set_to_none: bool = True) -> None:
+        """Call after every micro-batch's `backward()`: folds each present non-fp32 `p.grad` into its fp32 accumulator
+        (`acc = g.float()` on a parameter's first fold since the last step / `zero_grad()`, `acc += g.float()` afterwards, one fp32
+        add per element) and sets `p.grad = None`, so that the next backward moves its gradient in instead of adding to a stale one
+        (`set_to_none=False`: zeroed in place).  fp32 gradients are left alone: they already accumulate in fp32."""
+        if self.grad_accum_dtype is None:
+            raise RuntimeError("fused optimizer: accumulate_grads() needs grad_accum_dtype=torch.float32")
+        todo = [p for group in self.param_groups for p in group["params"] if self._unfolded(p)]
+        if not todo:
+            return
+        for p in todo:
+            self._check_tensor(p, p.grad)
+        self._ensure_accumulators(todo)
+        lib, stream = _lib.load(), _lib.current_stream_ptr(todo[0].device)
+        first = [p for p in todo if p not in self._acc_filled]
+        for overwrite, part in ((1, first), (0, [p for p in todo if p in self._acc_filled])):
+            if not part:
+                continue
+            table = (_lib.PrlAccumSegment * len(part))()  # the library cuts it into launches of 64 segments
+            for seg, p in zip(table, part):
+                seg.grad, seg.acc, seg.numel, seg.grad_dtype = p.grad.data_ptr(), self._acc[p].data_ptr(), p.numel(), _DTYPES[p.grad.dtype]
+            _lib.check(lib.prl_optim_grad_accumulate(table, len(part), overwrite, stream))
+        self._acc_filled.update(todo)
+        for p in todo:
+            if set_to_none:
+                p.grad = None  # (freed in stream order: the fold above has been enqueued)
+                self._acc_zeroed.pop(p, None)
+            else:
+                p.grad.zero_()
+                self._acc_zeroed[p] = (p.grad, p.grad._version)
+
+    @torch.no_grad()
+    def reduce_accumulated(self, group=None) -> None:
+        """Average the gradients over the data-parallel ranks in fp32: all_reduce(SUM) of the flat accumulator buffer and of every
+        fp32 `p.grad` that bypasses it, divided by the group size.  A slot that is empty on this rank contributes zeros; afterwards
+        every slot counts as having a gradient, so the ranks take identical steps.  RCCL reduces the device tensors; gloo stages them
+        through the host inside torch.distributed.  No-op without an initialised group or with one rank."""
+        import torch.distributed as dist
+
+        if self.grad_accum_dtype is None:
+            raise RuntimeError("fused optimizer: reduce_accumulated() needs grad_accum_dtype=torch.float32")
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        world = dist.get_world_size(group)
+        if world == 1:
+            return
+        self._check_all_folded()
+        self._ensure_accumulators()
+        for p, view in self._acc.items():
+            if p not in self._acc_filled:
+                view.zero_()
+        if self._acc_flat is not None:
+            dist.all_reduce(self._acc_flat, op=dist.ReduceOp.SUM, group=group)
+            self._acc_flat.div_(world)
+            self._acc_filled.update(self._acc)
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p in self._acc:
+                    continue
+                if p.grad is None:
+                    p.grad = torch.zeros_like(p, dtype=torch.float32)
+                dist.all_reduce(p.grad, op=dist.ReduceOp.SUM, group=group)
+                p.grad.div_(world)
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        """Clears `p.grad` as torch does and marks every accumulator empty (no memset: the next fold overwrites)."""
+        super().zero_grad(set_to_none=set_to_none)
+        self._acc_filled.clear()
+        self._acc_zeroed.clear()
+
     # ---- segment table ----------------------------------------------------------------------------------------------------
     def _check_tensor(self, p: torch.Tensor, g: torch.Tensor | None) -> None:
         _lib.require_device(p, g)
@@ -155,13 +292,13 @@ class _FusedOptimizer(torch.optim.Optimizer):
         entries = [(p, group) for group in self.param_groups for p in group["params"]]
         devices = {p.device for p, _ in entries}
         for p, _ in entries:
-            self._check_tensor(p, p.grad)
+            self._check_tensor(p, self._grad_of(p))
         if len(devices) > 1:
             raise ValueError(f"fused optimizer: all parameters must live on one device (got {sorted(map(str, devices))})")
         self._ensure_state()
         table = (_lib.PrlOptimSegment * max(len(entries), 1))()
         for seg, (p, _) in zip(table, entries):
-            g = p.grad
+            g = self._grad_of(p)
             st = self.state[p] if g is not None else {}
             seg.param, seg.numel, seg.param_dtype = p.data_ptr(), p.numel(), _DTYPES[p.dtype]
             seg.grad = g.data_ptr() if g is not None and p.numel() else None
@@ -181,9 +318,9 @@ class _FusedOptimizer(torch.optim.Optimizer):
             if self._workspace is None or self._workspace.numel() < need.value:
                 self._workspace = torch.empty(max(need.value, 8), dtype=torch.uint8, device=device)
 
-    @staticmethod
-    def _key(entries) -> list[tuple[int, int]]:
-        return [(p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p, _ in entries]
+    def _key(self, entries) -> list[tuple]:
+        grads = [self._grad_of(p) for p, _ in entries]  # an accumulator where one is filled: another address AND another dtype
+        return [(p.data_ptr(), 0 if g is None else g.data_ptr(), None if g is None else g.dtype) for (p, _), g in zip(entries, grads)]
 
     def _current_table(self):
         entries = [(p, group) for group in self.param_groups for p in group["params"]]
@@ -202,6 +339,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         step's value after the next norm pass; the caller decides when to `float()` it).
         `max_norm` None or <= 0 reports the norm and clips nothing."""
         lib = _lib.load()
+        self._check_all_folded()
         table, entries = self._current_table()
         if not entries:
             raise ValueError("fused optimizer: no parameters")
@@ -224,17 +362,19 @@ class _FusedOptimizer(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
+        self._check_all_folded()
         table, entries = self._current_table()
         if not entries:
             return loss
         for seg, (p, group) in zip(table, entries):
-            if p.grad is None:
+            if self._grad_of(p) is None:
                 continue
             st = self.state[p]
             st["step"] += 1
             seg.step = int(st["step"])
             seg.lr, seg.weight_decay = float(group["lr"]), float(group["weight_decay"])
         self._launch(lib, table, len(entries), self._record.data_ptr() if clipped else None)
+        self._acc_filled.clear()  # the next fold of every accumulator overwrites
         return loss
 
     def _launch(self, lib, table, n: int, record: int | None) -> None:
@@ -265,9 +405,9 @@ class FusedAdamW(_FusedOptimizer):
     _state_keys = ("exp_avg", "exp_avg_sq")
 
     def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 master_weights: bool = True):
+                 master_weights: bool = True, grad_accum_dtype: torch.dtype | None = None):
         _check_hyper(lr, betas, weight_decay, eps)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), master_weights)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), master_weights, grad_accum_dtype)
 
     def _launch_key(self, group):
         return (float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]))
@@ -281,9 +421,10 @@ class FusedLion(_FusedOptimizer):
 
     _state_keys = ("exp_avg",)
 
-    def __init__(self, params, lr: float = 1e-4, betas: tuple[float, float] = (0.9, 0.99), weight_decay: float = 0.0, master_weights: bool = True):
+    def __init__(self, params, lr: float = 1e-4, betas: tuple[float, float] = (0.9, 0.99), weight_decay: float = 0.0, master_weights: bool = True,
+                 grad_accum_dtype: torch.dtype | None = None):
         _check_hyper(lr, betas, weight_decay)
-        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay), master_weights)
+        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay), master_weights, grad_accum_dtype)
 
     def _launch_key(self, group):
         return (float(group["betas"][0]), float(group["betas"][1]))
@@ -292,11 +433,14 @@ class FusedLion(_FusedOptimizer):
         _lib.check(lib.prl_optim_lion_step(table, n, key[0], key[1], record, self._stream()))
 
 
-def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weight_decay: float):
-    """The reference's dispatch (:25-45) with its names; "adamw_torch" and "lion" are the fused HIP steps."""
+def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weight_decay: float, grad_accum_dtype: torch.dtype | None = None):
+    """The reference's dispatch (:25-45) with its names; "adamw_torch" and "lion" are the fused HIP steps.
+    `grad_accum_dtype=torch.float32`: fp32 gradient accumulation (the fused steps only)."""
     grouped_params = get_grouped_params(model, weight_decay)
+    if grad_accum_dtype is not None and name not in ("adamw_torch", "lion"):
+        raise ValueError(f'grad_accum_dtype needs a fused optimizer ("adamw_torch" or "lion"), not "{name}"')
     if name == "adamw_torch":
-        return FusedAdamW(grouped_params, lr=learning_rate)
+        return FusedAdamW(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype)
     if name == "adafactor":
         from transformers import Adafactor
 
@@ -308,5 +452,5 @@ def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weigh
             raise ImportError(f'optimizer "cpuadam" needs the deepspeed package: {e}') from e
         return deepspeed.ops.adam.DeepSpeedCPUAdam(grouped_params, lr=learning_rate)
     if name == "lion":
-        return FusedLion(grouped_params, lr=learning_rate)
+        return FusedLion(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype)
     raise ValueError(f"Unknown optimizer: {name}")

@@ -564,6 +564,9 @@ class LearnerStep:
         self.model, self.optimizer, self.lr_scheduler = model, optimizer, lr_scheduler
         self.rl_step_fn = rl_step_fn
         self.group = process_group
+        # fp32 gradient accumulation (finetune/optim.py): every pass runs unsynchronised and is folded into the optimizer's fp32
+        # accumulators, which are averaged over the ranks at the boundary (DDP would reduce the last micro-batch's p.grad only)
+        self.fp32_accumulation = getattr(optimizer, "grad_accum_dtype", None) is not None
         self.seq_parallel_group = seq_parallel_group
         self.distributed = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(process_group) if self.distributed else 1
@@ -658,7 +661,7 @@ class LearnerStep:
         self.total_samples = overcounted // self.seq_parallel
         do_optimizer_step = self.total_samples == self.target_samples
 
-        with self._sync_context(do_optimizer_step):
+        with self._sync_context(do_optimizer_step and not self.fp32_accumulation):
             if self.seq_parallel_group is not None:
                 loss, stats = self.rl_step_fn(self.model, batch, m.completed_steps, self.max_train_steps, self.rl_config,
                                               seq_parallel_group=self.seq_parallel_group)
@@ -670,6 +673,8 @@ class LearnerStep:
                 for k, v in stats.items():
                     self._rl_metrics[k].append(v)
             loss.backward()
+        if self.fp32_accumulation:
+            self.optimizer.accumulate_grads()
 
         self.publish(SamplesProcessed(samples_processed=self.start_samples + self.total_samples))
         result: dict[str, Any] = {"loss": loss.detach(), "did_optimizer_step": False, "stats": stats, "metrics": {}}
@@ -683,6 +688,8 @@ class LearnerStep:
         m.samples = self.start_samples + self.total_samples
         m.tokens += sum(self._tokens) * self.world
         assert sum(self._micro_batch_sizes) == self.samples_per_lead_per_step
+        if self.fp32_accumulation:
+            self.optimizer.reduce_accumulated(self.group)
         if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
             # fused boundary (finetune/optim.py): norm pass + step, the clip coefficient stays on the device; the norm is read
             # once both are enqueued
@@ -793,7 +800,7 @@ class StreamedLearnerStep(LearnerStep):
         self.total_samples = overcounted // self.seq_parallel
         do_optimizer_step = self.total_samples == self.target_samples
 
-        with self._sync_context(do_optimizer_step):
+        with self._sync_context(do_optimizer_step and not self.fp32_accumulation):
             sp = {"seq_parallel_group": self.seq_parallel_group} if self.seq_parallel_group is not None else {}  # (finetune_loop.py:768-775)
             loss, stats_dev = self.model(rl_batch=batch, rl_config=self.rl_config, current_step=m.completed_steps, max_step=self.max_train_steps, **sp)
             if is_sentinel:
@@ -802,6 +809,8 @@ class StreamedLearnerStep(LearnerStep):
                 self._stats_dev.append(stats_dev)
                 self._input_sizes.append(int(batch.input_ids.numel()))
             loss.backward()
+        if self.fp32_accumulation:
+            self.optimizer.accumulate_grads()
         self.publish(SamplesProcessed(samples_processed=self.start_samples + self.total_samples))
         result: dict[str, Any] = {"loss": loss.detach(), "did_optimizer_step": False, "stats": None, "metrics": {}}
         if not do_optimizer_step:
@@ -811,6 +820,8 @@ class StreamedLearnerStep(LearnerStep):
         _, kl_coef, ent_coef = make_loss_config(self.rl_config, m.completed_steps, self.max_train_steps)
         # fused boundary (finetune/optim.py): the norm pass runs first and its result rides in the ONE statistics copy below
         gn_dev = None
+        if self.fp32_accumulation:
+            self.optimizer.reduce_accumulated(self.group)
         if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
             gn_dev = self.optimizer.compute_grad_norm(self.gradient_clipping_threshold)
             if not self._stats_dev:
@@ -922,6 +933,7 @@ class NativeLearnerStep:
         self.max_train_steps = max_train_steps
         self.gradient_clipping_threshold = gradient_clipping_threshold
         self.group = process_group
+        self.fp32_accumulation = getattr(optimizer, "grad_accum_dtype", None) is not None  # see LearnerStep
         self.distributed = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(process_group) if self.distributed else 1
         self.rank = dist.get_rank(process_group) if self.distributed else 0
@@ -978,10 +990,13 @@ class NativeLearnerStep:
         vacc = None  # actor-critic: [value_mean, value_max, value_min, value_loss, value_mse] of the step so far (device, fp64)
         for j in range(n_passes):
             last = j == n_passes - 1
-            ctx = self.model.no_sync() if (hasattr(self.model, "no_sync") and not last) else contextlib.nullcontext()
+            sync = last and not self.fp32_accumulation
+            ctx = self.model.no_sync() if (hasattr(self.model, "no_sync") and not sync) else contextlib.nullcontext()
             if j >= n:  # this rank ran out of data: keep the collectives of the others company
                 with ctx:
                     self._sentinel_pass(rollouts.device)
+                if self.fp32_accumulation:
+                    self.optimizer.accumulate_grads()
                 continue
             b = batches[j]
             fused_ref = None
@@ -1026,11 +1041,15 @@ class NativeLearnerStep:
                     torch.autograd.backward([logits, values], [dlogits.to(logits.dtype), (self.rl_config.value_loss_coef * g_val).to(values.dtype)])
                 else:
                     logits.backward(dlogits.to(logits.dtype))
+            if self.fp32_accumulation:
+                self.optimizer.accumulate_grads()
         loss, stats = hp.finish()
         value_stats = None
         if self.has_value_head:
             value_stats = self._reduce_value_stats(vacc if vacc is not None else torch.zeros(5, dtype=torch.float64, device=rollouts.device))
             loss = loss + self.rl_config.value_loss_coef * value_stats[3].to(loss.dtype)
+        if self.fp32_accumulation:
+            self.optimizer.reduce_accumulated(self.group)
         if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
             # fused boundary (finetune/optim.py): nothing waits between the norm and the step; the norm is read once both are enqueued
             self.metrics.grad_norm = float(self.optimizer.clip_and_step(self.gradient_clipping_threshold))

@@ -9,6 +9,16 @@ HIP events around every boundary, >= 20 timed boundaries after warm-up.  Every c
 own under its own time limit; the first one that fails ends the run.  One JSON object on stdout and in --out.
 
     python scripts/optim_step_bench.py --out profiles/optim_step_bench.json
+
+`--mode grad_accum` times the fp32 gradient fold on the same list instead (the bf16 parameters; the fp32 head bypasses the accumulator):
+
+  fold_add         prl_optim_grad_accumulate, overwrite = 0: acc += g.float()         (2 + 4 read, 4 written = 10 B/element)
+  fold_overwrite   prl_optim_grad_accumulate, overwrite = 1: acc = g.float()          (2 read, 4 written = 6 B/element)
+  torch_add        per parameter `acc.add_(p.grad)` into preallocated fp32 tensors    (the stock equivalent of fold_add)
+
+all three in ONE child process on the same gradients, HIP events around each repetition, 20 repetitions after warm-up, median [min, max].
+
+    python scripts/optim_step_bench.py --mode grad_accum --out profiles/grad_accum_bench.json
 """
 
 from __future__ import annotations
@@ -96,6 +106,75 @@ def run_one(config: str, steps: int, warmup: int, max_norm: float) -> dict:
     return out
 
 
+def run_grad_accum(steps: int, warmup: int) -> dict:
+    import torch
+
+    from pipelinerl_amd import _lib
+    from pipelinerl_amd.weight_sync_probe import qwen25_shapes
+
+    dev = torch.device("cuda", 0)
+    shapes = [(n, s) for n, s in qwen25_shapes("7b") if n != "lm_head.weight"]
+    gen = torch.Generator(device=dev).manual_seed(0)
+    grads = [torch.empty(shape, dtype=torch.bfloat16, device=dev).normal_(0.0, 1e-3, generator=gen) for _, shape in shapes]
+    numel = sum(g.numel() for g in grads)
+    slots = [(-(-g.numel() // 16)) * 16 for g in grads]
+    flat = torch.zeros(sum(slots), dtype=torch.float32, device=dev)  # the optimizer's layout: one flat buffer, 64-byte aligned slots
+    table = (_lib.PrlAccumSegment * len(grads))()
+    off = 0
+    for seg, g, slot in zip(table, grads, slots):
+        seg.grad, seg.acc, seg.numel, seg.grad_dtype = g.data_ptr(), flat[off:off + g.numel()].data_ptr(), g.numel(), _lib.PRL_DTYPE_BF16
+        off += slot
+    stock = [torch.zeros(g.shape, dtype=torch.float32, device=dev) for g in grads]
+    lib, stream = _lib.load(), _lib.current_stream_ptr(dev)
+
+    def torch_add():
+        for a, g in zip(stock, grads):
+            a.add_(g)
+
+    calls = {"fold_add": lambda: _lib.check(lib.prl_optim_grad_accumulate(table, len(grads), 0, stream)),
+             "fold_overwrite": lambda: _lib.check(lib.prl_optim_grad_accumulate(table, len(grads), 1, stream)),
+             "torch_add": torch_add}
+    bytes_per_element = {"fold_add": 10, "fold_overwrite": 6, "torch_add": 10}
+    times = {k: [] for k in calls}
+    for k in range(warmup + steps):  # interleaved: the three see the same clocks
+        for name, call in calls.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            call()
+            b.record()
+            b.synchronize()
+            if k >= warmup:
+                times[name].append(a.elapsed_time(b))
+    # the two accumulators took the same folds in another order of calls: (warmup + steps) adds each, the flat one restarted by every overwrite
+    out = {"tensors": len(grads), "numel": numel, "steps": steps, "warmup": warmup, "results": {}}
+    for name, t in times.items():
+        med = statistics.median(t)
+        gbs = numel * bytes_per_element[name] / (med * 1e-3) / 1e9
+        out["results"][name] = {"median_ms": med, "min_ms": min(t), "max_ms": max(t), "bytes_per_element": bytes_per_element[name],
+                                "algorithmic_bytes": numel * bytes_per_element[name], "achieved_gbs": gbs, "frac_of_peak": gbs / PEAK_GBS,
+                                "frac_of_copy_ceiling": gbs / COPY_CEILING_GBS}
+    return out
+
+
+def main_grad_accum(args) -> None:
+    cmd = [sys.executable, __file__, "--one", "grad_accum", "--steps", str(args.steps), "--warmup", str(args.warmup)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
+    line = next((l for l in res.stdout.splitlines() if l.startswith("RESULT ")), None)
+    if res.returncode != 0 or line is None:
+        raise SystemExit(f"grad_accum: exit status {res.returncode}\n{res.stdout[-2000:]}\n{res.stderr[-4000:]}")
+    report = json.loads(line[len("RESULT "):])
+    r = report["results"]
+    spread = r["torch_add"]["max_ms"] - r["torch_add"]["min_ms"]
+    gain = r["torch_add"]["median_ms"] - r["fold_add"]["median_ms"]
+    report = {"workload": "Qwen2.5-7B parameter list without the fp32 lm_head: bf16 gradients folded into fp32 accumulators", **report,
+              "spread_torch_add_ms": spread, "fold_add_gain_ms": gain, "fold_is_faster_by_more_than_the_spread": gain > spread}
+    text = json.dumps(report, indent=1)
+    print(text)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(text + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -103,8 +182,15 @@ def main() -> None:
     ap.add_argument("--max-norm", type=float, default=0.3)
     ap.add_argument("--timeout", type=int, default=300, help="seconds per configuration")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--one", choices=CONFIGS, default=None, help="(child) run one configuration in this process")
+    ap.add_argument("--mode", choices=("boundary", "grad_accum"), default="boundary", help="what to time: the step boundary, or the fp32 gradient fold")
+    ap.add_argument("--one", choices=CONFIGS + ("grad_accum",), default=None, help="(child) run one configuration in this process")
     args = ap.parse_args()
+    if args.one == "grad_accum":
+        print("RESULT " + json.dumps(run_grad_accum(args.steps, args.warmup)), flush=True)
+        return
+    if args.mode == "grad_accum":
+        main_grad_accum(args)
+        return
     if args.one:
         print("RESULT " + json.dumps(run_one(args.one, args.steps, args.warmup, args.max_norm)), flush=True)
         return

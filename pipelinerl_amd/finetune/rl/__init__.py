@@ -512,11 +512,20 @@ def host_stats(stats_dev: torch.Tensor, input_size: int, kl_coef: float, ent_coe
     """The step's device statistics -> the reference's dict, with its runtime asserts: ONE device -> host copy.  `stats_dev`:
     double[32] of K2+K3, optionally followed by the value head's double[5] (then the reported and asserted loss is the
     combined one, rl/__init__.py:381-386, 399-401, and the five value keys close the dict, :441-448)."""
-    stats = stats_dev.cpu().tolist()  # the single device->host sync of the step
+    return stats_row_to_dict(stats_dev.cpu().tolist(), input_size, kl_coef, ent_coef, value_loss_coef)  # the single device->host sync of the step
+
+
+def combined_loss(policy_loss: float, value_loss: float, value_loss_coef: float) -> float:
+    """policy_loss + value_loss_coef * value_loss as the reference reports it (rl/__init__.py:381): added in fp32."""
+    return float(np.float32(policy_loss) + np.float32(value_loss_coef * np.float32(value_loss)))
+
+
+def stats_row_to_dict(stats: list[float], input_size: int, kl_coef: float, ent_coef: float, value_loss_coef: float = 0.0) -> dict[str, float]:
+    """The host half of `host_stats`: one row of 32 (+ 5) floats that is already on the host.  The loss lane of `stats` is replaced
+    by the combined loss when the value statistics are present."""
     vstats = stats[_lib.PRL_NUM_STATS:]
     if vstats:
-        combined = np.float32(stats[STAT_INDEX["loss"]]) + np.float32(value_loss_coef * np.float32(vstats[VALUE_STAT_KEYS.index("value_loss")]))
-        stats[STAT_INDEX["loss"]] = float(combined)
+        stats[STAT_INDEX["loss"]] = combined_loss(stats[STAT_INDEX["loss"]], vstats[VALUE_STAT_KEYS.index("value_loss")], value_loss_coef)
     check_finite(stats)
     if int(stats[STAT_INDEX["num_output_tokens_sum"]]) == 0:
         return {"input_size": float(input_size)}

@@ -532,7 +532,91 @@ def _barrier() -> None:
 # ---------------------------------------------------------------------------------------------
 
 
-class LearnerStep:
+class _LearnerBase:
+    """What every learner step shares: its place among the data-parallel ranks, the trainer stream, the weight-update rule and
+    the optimizer boundary."""
+
+    def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, lr_scheduler: Any, gradient_clipping_threshold: float | None,
+                 process_group: Any, training_metrics: TrainingMetrics | None, weight_update_manager: WeightUpdateManager | None,
+                 weight_update_interval: int, send_weight_updates: bool, trainer_stream: SingleStreamSpec | None):
+        import torch.distributed as dist
+
+        self.model, self.optimizer, self.lr_scheduler = model, optimizer, lr_scheduler
+        self.gradient_clipping_threshold = gradient_clipping_threshold
+        self.group = process_group
+        # fp32 gradient accumulation (finetune/optim.py): every pass runs unsynchronised and is folded into the optimizer's fp32
+        # accumulators, which are averaged over the ranks at the boundary (DDP would reduce the last micro-batch's p.grad only)
+        self.fp32_accumulation = getattr(optimizer, "grad_accum_dtype", None) is not None
+        self.distributed = dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size(process_group) if self.distributed else 1
+        self.rank = dist.get_rank(process_group) if self.distributed else 0
+        self.metrics = training_metrics or TrainingMetrics()
+        self.weight_update_manager = weight_update_manager
+        self.weight_update_interval = weight_update_interval
+        self.send_weight_updates = send_weight_updates
+        self._writer_cm = self._writer = None
+        if trainer_stream is not None and self.rank == 0:
+            self._writer_cm = write_to_streams(trainer_stream)
+            self._writer = self._writer_cm.__enter__()
+
+    @contextlib.contextmanager
+    def _sync_context(self, sync: bool):
+        if sync or not hasattr(self.model, "no_sync"):
+            yield
+        else:
+            with self.model.no_sync():
+                yield
+
+    def publish(self, message: BaseModel) -> None:
+        if self._writer is not None:
+            self._writer.write(message)
+
+    # -- the optimizer boundary, in two halves: a step may copy its statistics to the host between them --------------------------
+    def _reduce_and_norm(self) -> torch.Tensor | None:
+        """Average the fp32 accumulators over the ranks; with a fused optimizer (finetune/optim.py) and a threshold, enqueue the norm
+        pass and return the DEVICE norm - the clip coefficient stays on the device, the caller decides when to read the norm."""
+        if self.fp32_accumulation:
+            self.optimizer.reduce_accumulated(self.group)
+        if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
+            return self.optimizer.compute_grad_norm(self.gradient_clipping_threshold)
+        return None
+
+    def _apply_update(self, norm_dev: torch.Tensor | None, grad_norm: float | None = None) -> None:
+        """Clip, step, zero the gradients, advance the schedule.  `grad_norm`: the host value of `norm_dev` when the caller has
+        read it already; otherwise it is read once the step is enqueued."""
+        m = self.metrics
+        if norm_dev is not None:
+            self.optimizer.step(clipped=True)  # the coefficient of the norm pass, read on the device
+            m.grad_norm = float(norm_dev) if grad_norm is None else grad_norm
+        else:
+            if self.gradient_clipping_threshold is not None:
+                m.grad_norm = float(torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold))
+            self.optimizer.step()
+        self.optimizer.zero_grad()
+        if self.lr_scheduler is not None:
+            self.lr_scheduler.step()
+
+    def maybe_send_weights(self) -> bool:
+        """After an optimizer step: broadcast when enough samples were trained since the last
+        broadcast (`weight_update_interval`, reference :936-949).  Model version == samples trained."""
+        m = self.metrics
+        if not self.send_weight_updates or self.weight_update_manager is None:
+            return False
+        if m.samples - m.last_broadcasted_version < self.weight_update_interval:
+            return False
+        self.weight_update_manager.send_weight_update(m.samples)
+        m.last_broadcasted_version = m.samples
+        return True
+
+    def finish(self) -> None:
+        """Signal `TrainingDone` and close the trainer stream."""
+        self.publish(TrainingDone())
+        if self._writer_cm is not None:
+            self._writer_cm.__exit__(None, None, None)
+            self._writer_cm = self._writer = None
+
+
+class LearnerStep(_LearnerBase):
     """One data-parallel learner rank.  `step(batch)` consumes one micro-batch."""
 
     def __init__(
@@ -561,23 +645,12 @@ class LearnerStep:
         per-segment sums over the slices."""
         import torch.distributed as dist
 
-        self.model, self.optimizer, self.lr_scheduler = model, optimizer, lr_scheduler
+        super().__init__(model, optimizer, lr_scheduler, gradient_clipping_threshold, process_group, training_metrics,
+                         weight_update_manager, weight_update_interval, send_weight_updates, trainer_stream)
         self.rl_step_fn = rl_step_fn
-        self.group = process_group
-        # fp32 gradient accumulation (finetune/optim.py): every pass runs unsynchronised and is folded into the optimizer's fp32
-        # accumulators, which are averaged over the ranks at the boundary (DDP would reduce the last micro-batch's p.grad only)
-        self.fp32_accumulation = getattr(optimizer, "grad_accum_dtype", None) is not None
         self.seq_parallel_group = seq_parallel_group
-        self.distributed = dist.is_available() and dist.is_initialized()
-        self.world = dist.get_world_size(process_group) if self.distributed else 1
-        self.rank = dist.get_rank(process_group) if self.distributed else 0
         self.seq_parallel = seq_parallel
-        self.metrics = training_metrics or TrainingMetrics()
         self.max_train_steps = max_train_steps
-        self.weight_update_manager = weight_update_manager
-        self.weight_update_interval = weight_update_interval
-        self.send_weight_updates = send_weight_updates
-        self.gradient_clipping_threshold = gradient_clipping_threshold
         self.max_lag = max_lag
         self.train_batch_size = train_batch_size
 
@@ -598,11 +671,6 @@ class LearnerStep:
         self._micro_batch_sizes: list[int] = []
         self._tokens: list[int] = []
         self._lag: dict[str, int] = {}
-        self._writer_cm = None
-        self._writer = None
-        if trainer_stream is not None and self.rank == 0:
-            self._writer_cm = write_to_streams(trainer_stream)
-            self._writer = self._writer_cm.__enter__()
         self._counter_device = next(model.parameters()).device if any(True for _ in model.parameters()) else torch.device("cpu")
         # The per-micro-batch sample counter (finetune_loop.py:709) is summed over the ranks on the HOST.  Under RCCL a device tensor + `.item()`
         # would drain the GPU's queue once per micro-batch - the synchronisation `StreamedLearnerStep` exists to avoid - so the default
@@ -625,53 +693,56 @@ class LearnerStep:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self._counter_group)
         return int(t.item())
 
-    @contextlib.contextmanager
-    def _sync_context(self, sync: bool):
-        if sync or not hasattr(self.model, "no_sync"):
-            yield
-        else:
-            with self.model.no_sync():
-                yield
-
-    def publish(self, message: BaseModel) -> None:
-        if self._writer is not None:
-            self._writer.write(message)
-
-    # -- the step -------------------------------------------------------------------------------
-    def step(self, batch: PipelineBatchEncoding) -> dict[str, Any]:
-        """Consume one micro-batch.  Returns {"loss", "did_optimizer_step", "stats", "metrics"}."""
+    def _count(self, batch: PipelineBatchEncoding, is_sentinel: bool) -> bool:
+        """Account for the micro-batch (reference :674-713); True when it closes the optimizer step."""
         m = self.metrics
-        is_sentinel = bool(batch.sentinel)
         if self.local_samples == self.target_samples_per_lead:
             assert is_sentinel, "We should get a sentinel batch"
         if self.max_lag is not None and m.last_broadcasted_version - batch.model_version > self.max_lag:
             m.samples_too_old_to_train += self.train_batch_size
         self._lag["min_version"] = min(self._lag.get("min_version", batch.model_version), batch.model_version)
         self._lag["max_version"] = max(self._lag.get("max_version", batch.model_version), batch.model_version)
-
         if not is_sentinel:
             m.passes += 1
             n = get_batch_sequence_count(batch)
             self._micro_batch_sizes.append(n)
             self.local_samples += n
-            self._tokens.append(get_batch_token_count(batch))
-
+            self._tokens.append(self._token_count(batch))
         overcounted = self._sum_over_ranks(self.local_samples)
         assert overcounted % self.seq_parallel == 0
         self.total_samples = overcounted // self.seq_parallel
-        do_optimizer_step = self.total_samples == self.target_samples
+        return self.total_samples == self.target_samples
+
+    # -- what a subclass changes ----------------------------------------------------------------
+    def _token_count(self, batch: PipelineBatchEncoding) -> int:
+        return get_batch_token_count(batch)
+
+    def _forward(self, batch: PipelineBatchEncoding, is_sentinel: bool) -> tuple[torch.Tensor, dict | None]:
+        """(loss attached to the model's graph, the micro-batch's statistics on the host); a real micro-batch's statistics are
+        kept for the step's aggregation."""
+        sp = {"seq_parallel_group": self.seq_parallel_group} if self.seq_parallel_group is not None else {}
+        loss, stats = self.rl_step_fn(self.model, batch, self.metrics.completed_steps, self.max_train_steps, self.rl_config, **sp)
+        if not is_sentinel:
+            for k, v in stats.items():
+                self._rl_metrics[k].append(v)
+        return loss, stats
+
+    def _boundary_stats(self, result: dict[str, Any], norm_dev: torch.Tensor | None) -> float | None:
+        """Called between the two halves of the optimizer boundary: bring in whatever statistics of the step are still on the
+        device.  Returns the host value of `norm_dev` if it was read on the way."""
+        return None
+
+    # -- the step -------------------------------------------------------------------------------
+    def step(self, batch: PipelineBatchEncoding) -> dict[str, Any]:
+        """Consume one micro-batch.  Returns {"loss", "did_optimizer_step", "stats", "metrics"}."""
+        m = self.metrics
+        is_sentinel = bool(batch.sentinel)
+        do_optimizer_step = self._count(batch, is_sentinel)
 
         with self._sync_context(do_optimizer_step and not self.fp32_accumulation):
-            if self.seq_parallel_group is not None:
-                loss, stats = self.rl_step_fn(self.model, batch, m.completed_steps, self.max_train_steps, self.rl_config,
-                                              seq_parallel_group=self.seq_parallel_group)
-            else:
-                loss, stats = self.rl_step_fn(self.model, batch, m.completed_steps, self.max_train_steps, self.rl_config)
+            loss, stats = self._forward(batch, is_sentinel)
             if is_sentinel:
                 loss = loss * 0.0  # keeps every rank's forward/backward count equal, adds nothing
-            else:
-                for k, v in stats.items():
-                    self._rl_metrics[k].append(v)
             loss.backward()
         if self.fp32_accumulation:
             self.optimizer.accumulate_grads()
@@ -682,26 +753,15 @@ class LearnerStep:
             return result
 
         # ---- accumulation boundary: optimizer step (:810-857)
+        norm_dev = self._reduce_and_norm()
+        grad_norm = self._boundary_stats(result, norm_dev)
         self.target_samples_per_lead += self.samples_per_lead_per_step
         self.target_samples += self.samples_per_step
         m.completed_steps += 1
         m.samples = self.start_samples + self.total_samples
         m.tokens += sum(self._tokens) * self.world
         assert sum(self._micro_batch_sizes) == self.samples_per_lead_per_step
-        if self.fp32_accumulation:
-            self.optimizer.reduce_accumulated(self.group)
-        if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
-            # fused boundary (finetune/optim.py): norm pass + step, the clip coefficient stays on the device; the norm is read
-            # once both are enqueued
-            m.grad_norm = float(self.optimizer.clip_and_step(self.gradient_clipping_threshold))
-        else:
-            if self.gradient_clipping_threshold is not None:
-                gn = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold)
-                m.grad_norm = float(gn)
-            self.optimizer.step()
-        self.optimizer.zero_grad()
-        if self.lr_scheduler is not None:
-            self.lr_scheduler.step()
+        self._apply_update(norm_dev, grad_norm)
         result["did_optimizer_step"] = True
         result["metrics"] = self._aggregate_metrics()
         self._rl_metrics = defaultdict(list)
@@ -720,25 +780,6 @@ class LearnerStep:
         if all(k in avg for k in ("rl/ratio_new_old_sum", "rl/ratio_new_old_squared_sum", "rl/num_output_tokens_sum")):
             avg["rl/ess"] = effective_sample_size(avg)
         return avg
-
-    def maybe_send_weights(self) -> bool:
-        """After an optimizer step: broadcast when enough samples were trained since the last
-        broadcast (`weight_update_interval`, reference :936-949).  Model version == samples trained."""
-        m = self.metrics
-        if not self.send_weight_updates or self.weight_update_manager is None:
-            return False
-        if m.samples - m.last_broadcasted_version < self.weight_update_interval:
-            return False
-        self.weight_update_manager.send_weight_update(m.samples)
-        m.last_broadcasted_version = m.samples
-        return True
-
-    def finish(self) -> None:
-        """Signal `TrainingDone` and close the trainer stream."""
-        self.publish(TrainingDone())
-        if self._writer_cm is not None:
-            self._writer_cm.__exit__(None, None, None)
-            self._writer_cm = self._writer = None
 
 
 class StreamedLearnerStep(LearnerStep):
@@ -768,112 +809,52 @@ class StreamedLearnerStep(LearnerStep):
             raise TypeError("StreamedLearnerStep drives a model prepared with pipelinerl_amd.fused_head.install_fused_head")
         if self.seq_parallel != 1 and self.seq_parallel_group is None:
             # slices of a packed sequence (types.py:145-180) trained without their group would silently drop the sequence-parallel
-            # reduction of the sequence-level sums (rl/utils.py:194-206); the group is forwarded to the model's forward in `step`
+            # reduction of the sequence-level sums (rl/utils.py:194-206); the group is forwarded to the model's forward in `_forward`
             raise ValueError("StreamedLearnerStep with seq_parallel > 1 needs seq_parallel_group (the ranks that hold the slices of one sequence)")
         self._stats_dev: list[torch.Tensor] = []
         self._input_sizes: list[int] = []
         # per real micro-batch: samples trained so far - the batch's model version; the most recent 4096 (a run is unbounded)
         self.lag_samples: collections.deque[int] = collections.deque(maxlen=4096)
 
-    def step(self, batch: PipelineBatchEncoding) -> dict[str, Any]:
-        from .finetune.rl import VALUE_STAT_KEYS, check_finite, make_loss_config, stats_to_dict
-        from . import _lib
+    def _token_count(self, batch: PipelineBatchEncoding) -> int:
+        tokens = batch.model_extra.get("tokens") if hasattr(batch, "model_extra") else None
+        return int(tokens) if tokens is not None else get_batch_token_count(batch)
 
+    def _forward(self, batch: PipelineBatchEncoding, is_sentinel: bool) -> tuple[torch.Tensor, None]:
         m = self.metrics
-        is_sentinel = bool(batch.sentinel)
-        if self.local_samples == self.target_samples_per_lead:
-            assert is_sentinel, "We should get a sentinel batch"
-        if self.max_lag is not None and m.last_broadcasted_version - batch.model_version > self.max_lag:
-            m.samples_too_old_to_train += self.train_batch_size
-        self._lag["min_version"] = min(self._lag.get("min_version", batch.model_version), batch.model_version)
-        self._lag["max_version"] = max(self._lag.get("max_version", batch.model_version), batch.model_version)
+        sp = {"seq_parallel_group": self.seq_parallel_group} if self.seq_parallel_group is not None else {}  # (finetune_loop.py:768-775)
+        loss, stats_dev = self.model(rl_batch=batch, rl_config=self.rl_config, current_step=m.completed_steps, max_step=self.max_train_steps, **sp)
         if not is_sentinel:
-            m.passes += 1
-            n = get_batch_sequence_count(batch)
-            self._micro_batch_sizes.append(n)
-            self.local_samples += n
-            tokens = batch.model_extra.get("tokens") if hasattr(batch, "model_extra") else None
-            self._tokens.append(int(tokens) if tokens is not None else get_batch_token_count(batch))
+            self._stats_dev.append(stats_dev)
+            self._input_sizes.append(int(batch.input_ids.numel()))
             self.lag_samples.append(m.samples - int(batch.model_version))
-        overcounted = self._sum_over_ranks(self.local_samples)
-        assert overcounted % self.seq_parallel == 0
-        self.total_samples = overcounted // self.seq_parallel
-        do_optimizer_step = self.total_samples == self.target_samples
+        return loss, None
 
-        with self._sync_context(do_optimizer_step and not self.fp32_accumulation):
-            sp = {"seq_parallel_group": self.seq_parallel_group} if self.seq_parallel_group is not None else {}  # (finetune_loop.py:768-775)
-            loss, stats_dev = self.model(rl_batch=batch, rl_config=self.rl_config, current_step=m.completed_steps, max_step=self.max_train_steps, **sp)
-            if is_sentinel:
-                loss = loss * 0.0
-            else:
-                self._stats_dev.append(stats_dev)
-                self._input_sizes.append(int(batch.input_ids.numel()))
-            loss.backward()
-        if self.fp32_accumulation:
-            self.optimizer.accumulate_grads()
-        self.publish(SamplesProcessed(samples_processed=self.start_samples + self.total_samples))
-        result: dict[str, Any] = {"loss": loss.detach(), "did_optimizer_step": False, "stats": None, "metrics": {}}
-        if not do_optimizer_step:
-            return result
+    def _boundary_stats(self, result: dict[str, Any], norm_dev: torch.Tensor | None) -> float | None:
+        """The step's statistics in ONE copy; the norm of a fused boundary rides in it."""
+        from .finetune.rl import make_loss_config, stats_row_to_dict
 
-        # ---- accumulation boundary: the step's statistics in ONE copy, then the optimizer step (:810-857)
-        _, kl_coef, ent_coef = make_loss_config(self.rl_config, m.completed_steps, self.max_train_steps)
-        # fused boundary (finetune/optim.py): the norm pass runs first and its result rides in the ONE statistics copy below
-        gn_dev = None
-        if self.fp32_accumulation:
-            self.optimizer.reduce_accumulated(self.group)
-        if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
-            gn_dev = self.optimizer.compute_grad_norm(self.gradient_clipping_threshold)
-            if not self._stats_dev:
-                grad_norm = float(gn_dev)
-        if self._stats_dev:
-            if gn_dev is None:
-                rows = torch.stack(self._stats_dev).cpu().tolist()
-            else:
-                block = torch.stack(self._stats_dev)
-                flat = torch.cat([block.flatten(), gn_dev.to(block.dtype).reshape(1)]).cpu().tolist()
-                grad_norm = flat.pop()
-                rows = [flat[i * block.shape[1]:(i + 1) * block.shape[1]] for i in range(block.shape[0])]
-            for row, size in zip(rows, self._input_sizes):
-                vstats = row[_lib.PRL_NUM_STATS:]
-                if vstats:
-                    row[_lib.STAT_INDEX["loss"]] = float(np.float32(row[_lib.STAT_INDEX["loss"]]) + np.float32(
-                        self.rl_config.value_loss_coef * np.float32(vstats[VALUE_STAT_KEYS.index("value_loss")])))
-                check_finite(row)
-                if int(row[_lib.STAT_INDEX["num_output_tokens_sum"]]) == 0:
-                    stats = {"input_size": float(size)}
-                else:
-                    stats = stats_to_dict(row, kl_coef, ent_coef, size)
-                    stats.update({k: float(np.float32(v)) for k, v in zip(VALUE_STAT_KEYS, vstats)})
-                for k, v in stats.items():
-                    self._rl_metrics[k].append(v)
-            result["stats"] = stats
-        self._stats_dev, self._input_sizes = [], []
-        self.target_samples_per_lead += self.samples_per_lead_per_step
-        self.target_samples += self.samples_per_step
-        m.completed_steps += 1
-        m.samples = self.start_samples + self.total_samples
-        m.tokens += sum(self._tokens) * self.world
-        assert sum(self._micro_batch_sizes) == self.samples_per_lead_per_step
-        if gn_dev is not None:
-            m.grad_norm = grad_norm
-            self.optimizer.step(clipped=True)  # the coefficient of the norm pass above, read on the device
+        if not self._stats_dev:  # no real micro-batch on this rank: the norm alone
+            return None if norm_dev is None else float(norm_dev)
+        _, kl_coef, ent_coef = make_loss_config(self.rl_config, self.metrics.completed_steps, self.max_train_steps)
+        block = torch.stack(self._stats_dev)
+        grad_norm = None
+        if norm_dev is None:
+            rows = block.cpu().tolist()
         else:
-            if self.gradient_clipping_threshold is not None:
-                gn = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold)
-                m.grad_norm = float(gn)
-            self.optimizer.step()
-        self.optimizer.zero_grad()
-        if self.lr_scheduler is not None:
-            self.lr_scheduler.step()
-        result["did_optimizer_step"] = True
-        result["metrics"] = self._aggregate_metrics()
-        self._rl_metrics = defaultdict(list)
-        self._micro_batch_sizes, self._tokens, self._lag = [], [], {}
-        return result
+            flat = torch.cat([block.flatten(), norm_dev.to(block.dtype).reshape(1)]).cpu().tolist()
+            grad_norm = flat.pop()
+            rows = [flat[i * block.shape[1]:(i + 1) * block.shape[1]] for i in range(block.shape[0])]
+        for row, size in zip(rows, self._input_sizes):
+            stats = stats_row_to_dict(row, size, kl_coef, ent_coef, self.rl_config.value_loss_coef)
+            for k, v in stats.items():
+                self._rl_metrics[k].append(v)
+        result["stats"] = stats
+        self._stats_dev, self._input_sizes = [], []
+        return grad_norm
 
 
-class NativeLearnerStep:
+class NativeLearnerStep(_LearnerBase):
     """The MI355X-native optimizer step: consumes a whole step's rollouts at once.
 
         K5 + ONE K6 launch  ->  per micro-batch: model forward, fused logits kernel (loss gradient
@@ -902,68 +883,95 @@ class NativeLearnerStep:
                  gradient_clipping_threshold: float | None = None, process_group: Any = None,
                  ref_model: torch.nn.Module | None = None, training_metrics: TrainingMetrics | None = None,
                  weight_update_manager: WeightUpdateManager | None = None, weight_update_interval: int = 1,
-                 send_weight_updates: bool = True, trainer_stream: SingleStreamSpec | None = None,
-                 equalize_micro_batches: bool = True, fused_ref_head: bool = True, skip_unlabelled: bool = True):
+                 send_weight_updates: bool = True, trainer_stream: SingleStreamSpec | None = None, skip_unlabelled: bool = True):
         """`ref_model`: a frozen reference policy on this GPU.  When given, the KL-to-reference term
         uses ITS log-probabilities, computed per micro-batch right before the policy forward (SURVEY
         §8f-3: replaces the HTTP round trip to a second inference server for KL-enabled configs).
-        With `fused_ref_head` (default) a model in the Hugging Face layout (`.model` + bias-free `.lm_head`) is asked for
-        its hidden states and the head runs on the MFMA kernels (no `[T, V]` reference logits); other models, or
-        `fused_ref_head=False`, go through their logits and K1.
+        A model in the Hugging Face layout (`.model` + bias-free `.lm_head`, `fused_head.ref_head_for`) is asked for its hidden
+        states and the head runs on the MFMA kernels (no `[T, V]` reference logits); other models go through their logits and K1.
         `samples_per_step`: the GLOBAL number of samples per optimizer step (the loss normaliser).
-        `equalize_micro_batches`: pad with sentinel micro-batches up to the largest count over the ranks
+        Every rank runs as many passes as the rank with the most micro-batches, the missing ones as sentinel micro-batches
         (needed by ZeRO / FSDP; plain DDP only needs every rank to run at least one).
         `skip_unlabelled`: see `HotPathStep` - False keeps the reference's finiteness assert over every logits row (rl/__init__.py:213).
         An actor-critic model (`.value_head`, finetune/value_model.py; its forward also returns `.value` [B, L]) takes the value branch
         of `rl_step` per micro-batch (rl/__init__.py:162, 265-272, 367-381, 441-448; one `prl_value_head_fwd_bwd` launch): the advantages
         column of the step batch becomes rewards - V before the logits kernel reads it, the value loss's closed-form gradient goes
         back through `.value` next to d logits, and the five value statistics are accumulated over the step (`stats_dict`)."""
-        import torch.distributed as dist
-
+        super().__init__(model, optimizer, lr_scheduler, gradient_clipping_threshold, process_group, training_metrics,
+                         weight_update_manager, weight_update_interval, send_weight_updates, trainer_stream)
         self.has_value_head = getattr(_unwrap(model), "value_head", None) is not None
         self.skip_unlabelled = bool(skip_unlabelled)
-
-        self.model, self.optimizer, self.lr_scheduler = model, optimizer, lr_scheduler
         self.ref_model = ref_model
-        self.fused_ref_head = bool(fused_ref_head)
         self.rl_config = rl_config.model_copy()
         self.rl_config.batch_size = samples_per_step
         self.samples_per_step = samples_per_step
         self.eos_token_id = eos_token_id
         self.max_train_steps = max_train_steps
-        self.gradient_clipping_threshold = gradient_clipping_threshold
-        self.group = process_group
-        self.fp32_accumulation = getattr(optimizer, "grad_accum_dtype", None) is not None  # see LearnerStep
-        self.distributed = dist.is_available() and dist.is_initialized()
-        self.world = dist.get_world_size(process_group) if self.distributed else 1
-        self.rank = dist.get_rank(process_group) if self.distributed else 0
-        self.metrics = training_metrics or TrainingMetrics()
-        self.weight_update_manager = weight_update_manager
-        self.weight_update_interval = weight_update_interval
-        self.send_weight_updates = send_weight_updates
-        self.equalize = equalize_micro_batches
-        self._last = None
-        self._writer_cm = self._writer = None
-        if trainer_stream is not None and self.rank == 0:
-            self._writer_cm = write_to_streams(trainer_stream)
-            self._writer = self._writer_cm.__enter__()
+        self._last = self._last_value_stats = None
 
-    def publish(self, message: BaseModel) -> None:
-        if self._writer is not None:
-            self._writer.write(message)
+    def _gather(self, row: torch.Tensor, device: Any) -> torch.Tensor:
+        from .hotpath import all_gather_rows
+
+        return all_gather_rows(row, self.group, device)
 
     def _share_counts(self, n_micro_batches: int, n_samples: int, device) -> tuple[int, int]:
         """(largest micro-batch count over the ranks, total samples) - one all-gather of two integers."""
         if not self.distributed or self.world == 1:
             return n_micro_batches, n_samples
-        import torch.distributed as dist
-
-        gloo = dist.get_backend(self.group) == "gloo"
-        mine = torch.tensor([n_micro_batches, n_samples], dtype=torch.int64, device="cpu" if gloo else device)
-        everyone = torch.empty((self.world, 2), dtype=torch.int64, device=mine.device)
-        dist.all_gather_into_tensor(everyone, mine.unsqueeze(0), group=self.group)
-        everyone = everyone.cpu()
+        everyone = self._gather(torch.tensor([n_micro_batches, n_samples], dtype=torch.int64), device).cpu()
         return int(everyone[:, 0].max()), int(everyone[:, 1].sum())
+
+    def _reduce_value_stats(self, v: torch.Tensor) -> torch.Tensor:
+        """The five value statistics over the data-parallel ranks: sums for the additive ones, max / min for the extrema."""
+        if not self.distributed or self.world == 1:
+            return v
+        everyone = self._gather(v, v.device).to(v.device)
+        return torch.stack([everyone[:, 0].sum(), everyone[:, 1].max(), everyone[:, 2].min(), everyone[:, 3].sum(), everyone[:, 4].sum()])
+
+    def _annotate_ref(self, hp, j: int, b: PipelineBatchEncoding) -> None:
+        """Micro-batch j's `ref_logprobs` column from the frozen reference policy."""
+        from .fused_head import _hidden_states, ref_head_for
+
+        fused_ref = ref_head_for(self.ref_model)
+        with torch.no_grad():
+            if fused_ref is not None:  # hidden states -> MFMA head: the [T, V] reference logits are never written
+                hp.annotate_ref_logprobs_from_hidden(j, fused_ref[1], _hidden_states(fused_ref[0], b))
+                return
+            ref_logits = self.ref_model(input_ids=b.input_ids, attention_mask=b.attention_mask, position_ids=b.position_ids).logits
+            if ref_logits.dtype not in (torch.float32, torch.bfloat16) or not ref_logits.is_contiguous():
+                ref_logits = ref_logits.float().contiguous()
+            hp.annotate_ref_logprobs(j, ref_logits)
+
+    def _micro_batch(self, hp, j: int, b: PipelineBatchEncoding, vacc: torch.Tensor | None) -> torch.Tensor | None:
+        """Forward, fused logits kernel, backward for micro-batch j.  `vacc`: [value_mean, value_max, value_min, value_loss,
+        value_mse] of the step so far (actor-critic; device, fp64); returned with this micro-batch folded in."""
+        out = self.model(input_ids=b.input_ids, attention_mask=b.attention_mask, position_ids=b.position_ids)
+        logits = out.logits
+        g_val = None
+        if self.has_value_head:
+            from .finetune.rl import value_head_terms
+
+            values = out.value
+            _, adv, vstats, g_val = value_head_terms(hp.cfg, b, values.detach(), want_grad=True)
+            # advantages := rewards - V (rl/__init__.py:272), IN the step batch: the logits kernel below and the step's ONE
+            # statistics launch (`finish`) read this column
+            # (`.data`: every column of the step batch is a view of ONE block, so an in-place write through the tensor itself would
+            # bump the version counter the model's saved `input_ids` share with it and autograd would refuse the backward)
+            b.advantages.data.copy_(adv.reshape(b.advantages.shape))
+            if vacc is None:
+                vacc = vstats.clone()
+            else:
+                vacc = torch.stack([vacc[0] + vstats[0], torch.maximum(vacc[1], vstats[1]), torch.minimum(vacc[2], vstats[2]),
+                                    vacc[3] + vstats[3], vacc[4] + vstats[4]])
+        lg = logits.detach()
+        if lg.dtype not in (torch.float32, torch.bfloat16) or not lg.is_contiguous():
+            lg = lg.float().contiguous()
+        dlogits = hp.logits_backward(j, lg)
+        if g_val is not None:  # final_loss = policy_loss + value_loss_coef * value_loss (:381): both roots in one backward
+            torch.autograd.backward([logits, values], [dlogits.to(logits.dtype), (self.rl_config.value_loss_coef * g_val).to(values.dtype)])
+        else:
+            logits.backward(dlogits.to(logits.dtype))
+        return vacc
 
     def _sentinel_pass(self, device) -> None:
         """One zero-loss forward/backward (finetune_loop.py:784-786) so this rank takes part in the collectives."""
@@ -986,61 +994,16 @@ class NativeLearnerStep:
         n = len(batches)
         n_max, n_samples = self._share_counts(n, rollouts.n_seqs, rollouts.device)
         assert n_samples == self.samples_per_step, f"the ranks' shares hold {n_samples} samples, a step takes {self.samples_per_step}"
-        n_passes = max(n_max, 1) if self.equalize else max(n, 1)
-        vacc = None  # actor-critic: [value_mean, value_max, value_min, value_loss, value_mse] of the step so far (device, fp64)
+        n_passes = max(n_max, 1)
+        vacc = None
         for j in range(n_passes):
-            last = j == n_passes - 1
-            sync = last and not self.fp32_accumulation
-            ctx = self.model.no_sync() if (hasattr(self.model, "no_sync") and not sync) else contextlib.nullcontext()
-            if j >= n:  # this rank ran out of data: keep the collectives of the others company
-                with ctx:
+            if j < n and self.ref_model is not None:
+                self._annotate_ref(hp, j, batches[j])
+            with self._sync_context(j == n_passes - 1 and not self.fp32_accumulation):
+                if j < n:
+                    vacc = self._micro_batch(hp, j, batches[j], vacc)
+                else:  # this rank ran out of data: keep the collectives of the others company
                     self._sentinel_pass(rollouts.device)
-                if self.fp32_accumulation:
-                    self.optimizer.accumulate_grads()
-                continue
-            b = batches[j]
-            fused_ref = None
-            if self.ref_model is not None and self.fused_ref_head:
-                from .fused_head import _hidden_states, ref_head_for
-
-                fused_ref = ref_head_for(self.ref_model)
-            if fused_ref is not None:  # hidden states -> MFMA head: the [T, V] reference logits are never written
-                with torch.no_grad():
-                    hp.annotate_ref_logprobs_from_hidden(j, fused_ref[1], _hidden_states(fused_ref[0], b))
-            elif self.ref_model is not None:
-                with torch.no_grad():
-                    ref_logits = self.ref_model(input_ids=b.input_ids, attention_mask=b.attention_mask, position_ids=b.position_ids).logits
-                    if ref_logits.dtype not in (torch.float32, torch.bfloat16) or not ref_logits.is_contiguous():
-                        ref_logits = ref_logits.float().contiguous()
-                    hp.annotate_ref_logprobs(j, ref_logits)
-                    del ref_logits
-            with ctx:
-                out = self.model(input_ids=b.input_ids, attention_mask=b.attention_mask, position_ids=b.position_ids)
-                logits = out.logits
-                g_val = None
-                if self.has_value_head:
-                    from .finetune.rl import value_head_terms
-
-                    values = out.value
-                    _, adv, vstats, g_val = value_head_terms(hp.cfg, b, values.detach(), want_grad=True)
-                    # advantages := rewards - V (rl/__init__.py:272), IN the step batch: the logits kernel below and the step's ONE
-                    # statistics launch (`finish`) read this column
-                    # (`.data`: every column of the step batch is a view of ONE block, so an in-place write through the tensor itself would
-                    # bump the version counter the model's saved `input_ids` share with it and autograd would refuse the backward)
-                    b.advantages.data.copy_(adv.reshape(b.advantages.shape))
-                    if vacc is None:
-                        vacc = vstats.clone()
-                    else:
-                        vacc = torch.stack([vacc[0] + vstats[0], torch.maximum(vacc[1], vstats[1]), torch.minimum(vacc[2], vstats[2]),
-                                            vacc[3] + vstats[3], vacc[4] + vstats[4]])
-                lg = logits.detach()
-                if lg.dtype not in (torch.float32, torch.bfloat16) or not lg.is_contiguous():
-                    lg = lg.float().contiguous()
-                dlogits = hp.logits_backward(j, lg)
-                if g_val is not None:  # final_loss = policy_loss + value_loss_coef * value_loss (:381): both roots in one backward
-                    torch.autograd.backward([logits, values], [dlogits.to(logits.dtype), (self.rl_config.value_loss_coef * g_val).to(values.dtype)])
-                else:
-                    logits.backward(dlogits.to(logits.dtype))
             if self.fp32_accumulation:
                 self.optimizer.accumulate_grads()
         loss, stats = hp.finish()
@@ -1048,18 +1011,7 @@ class NativeLearnerStep:
         if self.has_value_head:
             value_stats = self._reduce_value_stats(vacc if vacc is not None else torch.zeros(5, dtype=torch.float64, device=rollouts.device))
             loss = loss + self.rl_config.value_loss_coef * value_stats[3].to(loss.dtype)
-        if self.fp32_accumulation:
-            self.optimizer.reduce_accumulated(self.group)
-        if self.gradient_clipping_threshold is not None and hasattr(self.optimizer, "clip_and_step"):
-            # fused boundary (finetune/optim.py): nothing waits between the norm and the step; the norm is read once both are enqueued
-            self.metrics.grad_norm = float(self.optimizer.clip_and_step(self.gradient_clipping_threshold))
-        else:
-            if self.gradient_clipping_threshold is not None:
-                self.metrics.grad_norm = float(torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gradient_clipping_threshold))
-            self.optimizer.step()
-        self.optimizer.zero_grad()
-        if self.lr_scheduler is not None:
-            self.lr_scheduler.step()
+        self._apply_update(self._reduce_and_norm())  # nothing waits between the norm and the step
         m = self.metrics
         m.completed_steps += 1
         m.passes += n
@@ -1069,48 +1021,14 @@ class NativeLearnerStep:
         self._last, self._last_value_stats = hp, value_stats
         return {"loss": loss, "stats": stats, "value_stats": value_stats, "micro_batches": n, "did_optimizer_step": True, "sentinel_passes": n_passes - n}
 
-    def _reduce_value_stats(self, v: torch.Tensor) -> torch.Tensor:
-        """The five value statistics over the data-parallel ranks: sums for the additive ones, max / min for the extrema."""
-        if not self.distributed or self.world == 1:
-            return v
-        import torch.distributed as dist
-
-        dev = v.device
-        mine = v.cpu() if dist.get_backend(self.group) == "gloo" else v
-        everyone = torch.empty((self.world, 5), dtype=v.dtype, device=mine.device)
-        dist.all_gather_into_tensor(everyone, mine.unsqueeze(0).contiguous(), group=self.group)
-        everyone = everyone.to(dev)
-        return torch.stack([everyone[:, 0].sum(), everyone[:, 1].max(), everyone[:, 2].min(), everyone[:, 3].sum(), everyone[:, 4].sum()])
-
-    def maybe_send_weights(self) -> bool:
-        """After `step()`: broadcast when enough samples were trained since the last broadcast
-        (`weight_update_interval`, reference :936-949).  Model version == samples trained."""
-        m = self.metrics
-        if not self.send_weight_updates or self.weight_update_manager is None:
-            return False
-        if m.samples - m.last_broadcasted_version < self.weight_update_interval:
-            return False
-        self.weight_update_manager.send_weight_update(m.samples)
-        m.last_broadcasted_version = m.samples
-        return True
-
-    def finish(self) -> None:
-        """Signal `TrainingDone` and close the trainer stream."""
-        self.publish(TrainingDone())
-        if self._writer_cm is not None:
-            self._writer_cm.__exit__(None, None, None)
-            self._writer_cm = self._writer = None
-
     def stats_dict(self, stats: torch.Tensor) -> dict[str, float]:
         """The step's statistics as the reference's dict; for an actor-critic model the reported loss is the combined one and the five
         value keys close the dict (rl/__init__.py:381-386, 441-448)."""
         out = self._last.stats_dict(stats)
-        v = getattr(self, "_last_value_stats", None)
-        if v is not None:
-            from .finetune.rl import VALUE_STAT_KEYS
+        if self._last_value_stats is not None:
+            from .finetune.rl import VALUE_STAT_KEYS, combined_loss
 
-            vs = [float(np.float32(x)) for x in v.cpu().tolist()]
-            combined = float(np.float32(out["loss"]) + np.float32(self.rl_config.value_loss_coef * np.float32(vs[VALUE_STAT_KEYS.index("value_loss")])))
-            out["loss"] = out["max_loss"] = out["min_loss"] = combined
+            vs = [float(np.float32(x)) for x in self._last_value_stats.cpu().tolist()]
+            out["loss"] = out["max_loss"] = out["min_loss"] = combined_loss(out["loss"], vs[VALUE_STAT_KEYS.index("value_loss")], self.rl_config.value_loss_coef)
             out.update(dict(zip(VALUE_STAT_KEYS, vs)))
         return out

@@ -41,6 +41,17 @@ _MAX_LANES = [_lib.STAT_INDEX[k] for k in ("max_reward", "max_advantage", "max_k
 _MIN_LANES = [_lib.STAT_INDEX[k] for k in ("min_reward", "min_advantage", "min_kl", "min_token_weight")]
 
 
+def all_gather_rows(row: torch.Tensor, group: Any, device: Any) -> torch.Tensor:
+    """One small row per rank -> [world, n] with every rank's row, where the collective ran: on the HOST under gloo (CPU
+    collectives: tests, single-GPU dry runs - the row is staged through it), on `device` under RCCL."""
+    import torch.distributed as dist
+
+    row = row.to("cpu" if dist.get_backend(group) == "gloo" else device)
+    gathered = torch.empty((dist.get_world_size(group), row.numel()), dtype=row.dtype, device=row.device)
+    dist.all_gather_into_tensor(gathered, row.unsqueeze(0).contiguous(), group=group)
+    return gathered
+
+
 @dataclass
 class StepBuffers:
     """Step-long token-aligned buffers that the per-micro-batch logits kernel fills."""
@@ -190,13 +201,7 @@ class HotPathStep:
 
         if self.group is None and not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
             return stats
-        world = dist.get_world_size(self.group)
-        dev = stats.device
-        if dist.get_backend(self.group) == "gloo":  # CPU collectives (tests / single-GPU dry runs)
-            stats = stats.cpu()
-        gathered = torch.empty((world, stats.numel()), dtype=stats.dtype, device=stats.device)
-        dist.all_gather_into_tensor(gathered, stats.unsqueeze(0).contiguous(), group=self.group)
-        gathered = gathered.to(dev)
+        gathered = all_gather_rows(stats, self.group, stats.device).to(stats.device)
         out = gathered.sum(dim=0)
         out[_MAX_LANES] = gathered[:, _MAX_LANES].max(dim=0).values
         out[_MIN_LANES] = gathered[:, _MIN_LANES].min(dim=0).values

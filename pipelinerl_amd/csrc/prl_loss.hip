@@ -99,10 +99,14 @@ struct Acc {
   float s[P_NUM_ADD];
   float mx[4];
   float mn[4];
+  // bit i: a labelled token's reward / advantage / kl / weight was NaN.  torch's max() / min() return NaN then
+  // (reference :403-434) while fmaxf / fminf drop it; only the branchy path can meet one (the FAST probe is NaN there)
+  uint32_t nan_seen;
 };
 
 __device__ __forceinline__ void acc_init(Acc& a) {
   a.loss = 0.0;
+  a.nan_seen = 0u;
 #pragma unroll
   for (int i = 0; i < P_NUM_ADD; ++i) a.s[i] = 0.0f;
 #pragma unroll
@@ -208,6 +212,7 @@ __device__ __forceinline__ void token_step(const LossArgs& a, Acc& acc, bool val
     acc.s[P_CLAMP_NO] += per_label(o.clamp_no, inv_nl);
     acc.s[P_TW] += per_label(o.w, inv_nl);
     acc.s[P_N_MASKED] += 1.0f;
+    acc.nan_seen |= (reward != reward ? 1u : 0u) | (adv != adv ? 2u : 0u) | (o.kl != o.kl ? 4u : 0u) | (o.w != o.w ? 8u : 0u);
   }
   const float ninf = -INFINITY, pinf = INFINITY;
   acc.mx[0] = fmaxf(acc.mx[0], m ? reward : ninf);
@@ -220,6 +225,10 @@ __device__ __forceinline__ void token_step(const LossArgs& a, Acc& acc, bool val
   acc.mn[3] = fminf(acc.mn[3], m ? o.w : pinf);
 }
 
+// max / min that keep a NaN, like torch's reductions
+__device__ __forceinline__ double max_nan(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
+__device__ __forceinline__ double min_nan(double a, double b) { return (a != a || b != b) ? a + b : fmin(a, b); }
+
 __device__ __forceinline__ void block_reduce_store(const Acc& acc, double* out) {
   __shared__ double lds[kWavesPerBlock][P_NUM];
   const int lane = threadIdx.x & (kWave - 1);
@@ -229,13 +238,17 @@ __device__ __forceinline__ void block_reduce_store(const Acc& acc, double* out) 
     double v = prl::wave_sum(i == P_LOSS ? acc.loss : (double)acc.s[i]);
     if (lane == 0) lds[wid][i] = v;
   }
+  uint32_t nan_seen = acc.nan_seen;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nan_seen |= (uint32_t)__shfl_xor((int)nan_seen, o, 64);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     float vx = prl::wave_max(acc.mx[i]);
     float vn = prl::wave_min(acc.mn[i]);
     if (lane == 0) {
-      lds[wid][P_MAX_REWARD + i] = (double)vx;
-      lds[wid][P_MIN_REWARD + i] = (double)vn;
+      const bool nan = (nan_seen >> i) & 1u;
+      lds[wid][P_MAX_REWARD + i] = nan ? (double)NAN : (double)vx;
+      lds[wid][P_MIN_REWARD + i] = nan ? (double)NAN : (double)vn;
     }
   }
   __syncthreads();
@@ -248,9 +261,9 @@ __device__ __forceinline__ void block_reduce_store(const Acc& acc, double* out) 
       if (i < P_NUM_ADD) {
         v += o;
       } else if (i < P_MIN_REWARD) {
-        v = fmax(v, o);
+        v = max_nan(v, o);
       } else {
-        v = fmin(v, o);
+        v = min_nan(v, o);
       }
     }
     out[i] = v;
@@ -388,8 +401,8 @@ constexpr int kFinalLanes = kFinalBlock / P_NUM;  // 32
 
 __device__ __forceinline__ double combine(int i, double a, double b) {
   if (i < P_NUM_ADD) return a + b;
-  if (i < P_MIN_REWARD) return fmax(a, b);
-  return fmin(a, b);
+  if (i < P_MIN_REWARD) return max_nan(a, b);
+  return min_nan(a, b);
 }
 
 __global__ __launch_bounds__(kFinalBlock) void grpo_loss_finalize_kernel(const double* partials,

@@ -20,6 +20,7 @@ import torch
 from oracle import rl_loss as orl
 
 import grad_checks as gc
+import token_term_checks as tc
 from helpers import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -347,6 +348,7 @@ def test_step_scale_loss_launch_vs_oracle(libprl, cuda_device, n_mb):
     rng = np.random.default_rng(11)
     cols: dict[str, list] = {}
     tot_loss, agg = 0.0, {}
+    wit = {"loss": 0.0, "loss_scale": 0.0, "stats": {k: 0.0 for k in tc.SUM_STATS}, "scale": {k: 0.0 for k in tc.SUM_STATS}}
     for j in range(n_mb):
         # 1-3 sequences per micro-batch, prompts masked
         cuts = sorted(rng.choice(np.arange(256, T - 256), size=int(rng.integers(0, 3)), replace=False).tolist())
@@ -368,6 +370,16 @@ def test_step_scale_loss_launch_vs_oracle(libprl, cuda_device, n_mb):
         ent = rng.uniform(0, 3, (1, T)).astype(np.float32)
         res = orl.token_loss(b, nlp[:, 1:], ent[:, 1:], cfg_d, 0, 10, True)
         tot_loss += float(res["loss"])
+        # the fp64 witness of tests/token_term_checks.py per micro-batch (its column 0 is the flat launch's invalid sequence start).  No guard
+        # band: at epsilon = 0.02 random ratios do touch the bounds; a token within fp32 rounding of one moves the clip statistic by
+        # 1 / num_labels, ~1e-6 of its sum here
+        w = tc.witness(cfg_d, labels=labels, new_logprobs=nlp, entropy=ent, position_ids=pos, guard=False,
+                       **{c: b[c] for c in ("old_logprobs", "ref_logprobs", "advantages", "rewards", "group_tokens", "num_labels", "overflow")})
+        wit["loss"] += w.loss
+        wit["loss_scale"] += w.loss_scale
+        for k in tc.SUM_STATS:
+            wit["stats"][k] += w.stats[k]
+            wit["scale"][k] += w.stat_scale[k]
         for k, v in res["stats"].items():
             agg.setdefault(k, []).append(float(v))
         for k, v in b.items():
@@ -391,6 +403,13 @@ def test_step_scale_loss_launch_vs_oracle(libprl, cuda_device, n_mb):
               "ratio_ref_old", "clamp_log_ratio_ref_new_indicator", "clamp_log_ratio_new_old_indicator", "token_weight"):
         w = sum(agg[k])
         assert abs(s[SI[k]] - w) <= FP_TOL * max(abs(w), 1.0), (k, s[SI[k]], w)
+        # and against the size of its own terms: max(|w|, 1) alone lets `kl` or `token_weight` (1e-3 .. 1e-5) be wrong by more than their value
+        err = abs(s[SI[k]] - wit["stats"][k]) / wit["scale"][k] if wit["scale"][k] else float(s[SI[k]] != 0)
+        print(f"[token] step launch {k}: {err:.3e} (bound {tc.STAT_BOUND:.1e})")
+        assert err <= tc.STAT_BOUND, (k, s[SI[k]], wit["stats"][k], wit["scale"][k])
+    err = abs(s[SI["loss"]] - wit["loss"]) / wit["loss_scale"]
+    print(f"[token] step launch loss: {err:.3e} (bound {tc.LOSS_BOUND:.1e})")
+    assert err <= tc.LOSS_BOUND
     for k in ("max_reward", "max_advantage", "max_kl", "max_token_weight"):
         assert abs(s[SI[k]] - max(agg[k])) <= 1e-6 * max(abs(max(agg[k])), 1.0), k
     for k in ("min_reward", "min_advantage", "min_kl", "min_token_weight"):

@@ -12,6 +12,7 @@ from oracle import preprocess as opre
 from oracle import rl_loss as orl
 
 import grad_checks as gc
+import token_term_checks as tc
 from helpers import (
     PREPROCESS_CASES,
     RL_STEP_CASES,
@@ -298,6 +299,7 @@ def test_pack_edge_cases(libprl, cuda_device):
 def test_loss_kernel_unaligned_and_tail(libprl, cuda_device):
     """K2+K3 on views that defeat the 16-byte vector path and on lengths with a tail (n % 4 != 0):
     both paths must agree with the oracle."""
+    from pipelinerl_amd._lib import STAT_INDEX
     from pipelinerl_amd.finetune.rl import RLConfig, grpo_loss_from_logprobs, make_loss_config
 
     case = load_rl_case("c1_ppo_kl_temp")
@@ -334,6 +336,14 @@ def test_loss_kernel_unaligned_and_tail(libprl, cuda_device):
             s = stats.cpu().numpy()
             assert int(s[1]) == want["stats"]["num_output_tokens_sum"]
             assert int(s[2]) == want["num_sequences"]
+            # and every statistic against the size of its own terms (tests/token_term_checks.py), not max(|want|, 1)
+            k = orl.linear_decay(cur, mx, cfg.kl_coef, cfg.final_kl_coef)
+            w = tc.witness(dict(case["config"], kl_coef=k, final_kl_coef=k), labels=nb["labels"], new_logprobs=a_nlp, entropy=a_ent,
+                           position_ids=nb["position_ids"], **{c: nb[c] for c in ("old_logprobs", "ref_logprobs", "advantages", "rewards",
+                                                                                  "group_tokens", "num_labels", "overflow")})
+            rs = tc.check_stats({name: s[i] for name, i in STAT_INDEX.items()}, w)
+            print(f"[token] cut {cut} misalign {misalign}: {rs} (bounds {tc.STAT_BOUND:.1e} / {tc.LOSS_BOUND:.1e} / {tc.TOKEN_BOUND:.1e})")
+            assert rs.ok(), str(rs)
 
 
 def test_loss_nonfinite_raises(libprl, cuda_device):

@@ -99,12 +99,19 @@ __global__ __launch_bounds__(kBlock) void seq_scan_kernel(
 // group.  fp64 like the reference's pandas path.  One WAVE per key / per group: the members'
 // values are loaded by the 64 lanes at once (one lane per member: two dependent loads deep instead
 // of 3 x n), then every lane adds them up in DATASET ORDER out of its neighbours' registers
-// (`__shfl`), so the sums are the ones a single lane walking the members would form - the results
+// (`__shfl`), so the sums are the ones a single lane walking the members would form (compensated, below) - the results
 // do not depend on the launch geometry.  Keys larger than a wave are walked in chunks of 64.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double ordered_wave_sum(double acc, double v, int count) {
-  for (int j = 0; j < count; ++j) acc += __shfl(v, j, kWave);
-  return acc;
+// Compensated (Neumaier): `c` collects what each addition rounds away, the caller's sum is `s + c`.  A plain sum of 200 rewards is a
+// few ulp of its partial sums off; pandas' group sum is compensated and the leave-one-out mean of a member divides that error by
+// n - 1 but keeps it against the member's own small terms.  Built with -ffp-contract=off and no fast-math, so the terms stay.
+__device__ __forceinline__ void ordered_wave_sum(double& s, double& c, double v, int count) {
+  for (int j = 0; j < count; ++j) {
+    const double x = __shfl(v, j, kWave);
+    const double t = s + x;
+    c += (fabs(s) >= fabs(x)) ? (s - t) + x : (x - t) + s;
+    s = t;
+  }
 }
 
 __global__ __launch_bounds__(kBlock) void group_adv_kernel(
@@ -119,21 +126,23 @@ __global__ __launch_bounds__(kBlock) void group_adv_kernel(
   if (w < n_keys) {
     const int b = key_off[w], e = key_off[w + 1];
     const int n = e - b;
-    double sum = 0.0;
+    double sum = 0.0, sum_c = 0.0;
     for (int c = b; c < e; c += kWave) {
       const int i = c + lane;
       const double v = i < e ? reward[key_members[i]] : 0.0;
-      sum = ordered_wave_sum(sum, v, min(kWave, e - c));
+      ordered_wave_sum(sum, sum_c, v, min(kWave, e - c));
     }
+    sum += sum_c;
     double sd = 0.0;  // nan_to_num(std): NaN for singleton keys -> 0
     if (n > 1) {
       const double mean = sum / (double)n;
-      double ss = 0.0;
+      double ss = 0.0, ss_c = 0.0;
       for (int c = b; c < e; c += kWave) {
         const int i = c + lane;
         const double d = i < e ? reward[key_members[i]] - mean : 0.0;
-        ss = ordered_wave_sum(ss, d * d, min(kWave, e - c));
+        ordered_wave_sum(ss, ss_c, d * d, min(kWave, e - c));
       }
+      ss += ss_c;
       sd = sqrt(ss / (double)(n - 1));  // pandas std, ddof = 1
     }
     for (int i = b + lane; i < e; i += kWave) {

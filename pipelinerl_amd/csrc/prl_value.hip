@@ -49,6 +49,17 @@ __device__ __forceinline__ float load_value<uint16_t>(const void* p, int64_t i) 
   return __uint_as_float((uint32_t) static_cast<const uint16_t*>(p)[i] << 16);  // bf16 -> fp32 is exact
 }
 
+// value_max / value_min are the reference's `value_predictions[masks_shifted].max()` / `.min()` (:443-444): NaN as soon as one
+// labelled prediction is NaN.  fmax / fmin return the other operand, so every fold - lane, wave, block, grid - goes through these.
+template <class T>
+__device__ __forceinline__ T max_nan(T a, T b) {
+  return (a != a || b != b) ? a + b : (a > b ? a : b);
+}
+template <class T>
+__device__ __forceinline__ T min_nan(T a, T b) {
+  return (a != a || b != b) ? a + b : (a < b ? a : b);
+}
+
 template <class VT>
 __global__ __launch_bounds__(kBlock) void value_head_partial_kernel(ValueArgs a) {
   double s_mean = 0.0, s_loss = 0.0, s_mse = 0.0, s_cnt = 0.0;
@@ -78,8 +89,8 @@ __global__ __launch_bounds__(kBlock) void value_head_partial_kernel(ValueArgs a)
       s_mean += (double)prl_nan_to_num0(v / nl);
       s_mse += (double)prl_nan_to_num0(sq / nl);
       s_cnt += 1.0;
-      mx = fmaxf(mx, v);
-      mn = fminf(mn, v);
+      mx = max_nan(mx, v);
+      mn = min_nan(mn, v);
     }
     if (a.g_value) a.g_value[i] = g;
   }
@@ -89,8 +100,11 @@ __global__ __launch_bounds__(kBlock) void value_head_partial_kernel(ValueArgs a)
   s_loss = prl::wave_sum(s_loss);
   s_mse = prl::wave_sum(s_mse);
   s_cnt = prl::wave_sum(s_cnt);
-  mx = prl::wave_max(mx);
-  mn = prl::wave_min(mn);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mx = max_nan(mx, __shfl_xor(mx, o, 64));
+    mn = min_nan(mn, __shfl_xor(mn, o, 64));
+  }
   if (lane == 0) {
     red[wave][V_MEAN] = s_mean;
     red[wave][V_LOSS] = s_loss;
@@ -103,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void value_head_partial_kernel(ValueArgs a)
   if (threadIdx.x <= V_MIN) {
     const int e = threadIdx.x;
     double r = red[0][e];
-    for (int k = 1; k < kWaves; ++k) r = e < V_NUM_ADD ? r + red[k][e] : (e == V_MAX ? fmax(r, red[k][e]) : fmin(r, red[k][e]));
+    for (int k = 1; k < kWaves; ++k) r = e < V_NUM_ADD ? r + red[k][e] : (e == V_MAX ? max_nan(r, red[k][e]) : min_nan(r, red[k][e]));
     a.partials[(int64_t)blockIdx.x * V_NUM + e] = r;
   }
 }
@@ -116,15 +130,15 @@ __global__ __launch_bounds__(kWave) void value_head_finalize_kernel(const double
     const double* p = partials + (int64_t)b * V_NUM;
 #pragma unroll
     for (int e = 0; e < V_NUM_ADD; ++e) acc[e] += p[e];
-    mx = fmax(mx, p[V_MAX]);
-    mn = fmin(mn, p[V_MIN]);
+    mx = max_nan(mx, p[V_MAX]);
+    mn = min_nan(mn, p[V_MIN]);
   }
 #pragma unroll
   for (int e = 0; e < V_NUM_ADD; ++e) acc[e] = prl::wave_sum(acc[e]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    mx = fmax(mx, __shfl_xor(mx, o, 64));
-    mn = fmin(mn, __shfl_xor(mn, o, 64));
+    mx = max_nan(mx, __shfl_xor(mx, o, 64));
+    mn = min_nan(mn, __shfl_xor(mn, o, 64));
   }
   if (threadIdx.x == 0) {
     const bool any = acc[V_COUNT] > 0.0;  // "if masks_shifted.any() else 0.0" (:443-444)

@@ -12,6 +12,8 @@ import torch
 
 from oracle import rl_loss as orl
 
+import value_term_checks as vc
+
 pytestmark = pytest.mark.gpu
 
 FP_TOL = 1e-4
@@ -81,6 +83,10 @@ def test_value_head_kernel_vs_oracle(libprl, cuda_device, T, group_normalization
     # oracle's g_value = d loss / d value = coef * d value_loss / d value
     np.testing.assert_allclose(config["value_loss_coef"] * g_val.cpu().numpy().astype(np.float64), want["g_value"], rtol=1e-5, atol=1e-12)
     assert np.count_nonzero(g_val.cpu().numpy()[0, :-1][b["labels"][0, 1:] == -100]) == 0 and g_val[0, -1].item() == 0.0
+    # and against the fp64 witness, each statistic by the size of its own terms (tests/value_term_checks.py)
+    w = vc.witness(config, value=value, **vc.columns(b))
+    rs, rg = vc.check_stats(got, w, loss_out=vloss.item()), vc.check_grad(g_val.cpu().numpy(), w)
+    assert rs.ok() and rg.ok(), f"{rs}; {rg}"
 
 
 def test_value_head_non_finite_and_unlabelled(libprl, cuda_device):
@@ -100,6 +106,9 @@ def test_value_head_non_finite_and_unlabelled(libprl, cuda_device):
     got = dict(zip(VALUE_STAT_KEYS, vstats.cpu().tolist()))
     for k in ("value_loss", "value_mse", "value_mean"):
         assert np.isfinite(got[k]) and abs(got[k] - want["stats"][k]) <= FP_TOL * max(1.0, abs(want["stats"][k])), k
+    # `value_predictions[masks_shifted].max()` of a tensor that holds a NaN is NaN (reference rl/__init__.py:443-444)
+    assert np.isnan(want["stats"]["value_max"]) and np.isnan(want["stats"]["value_min"])
+    assert np.isnan(got["value_max"]) and np.isnan(got["value_min"]), got
     g = g_val.cpu().numpy()
     assert g[0, lab[3]] == 0.0 and g[0, lab[7]] == 0.0 and want["g_value"][0, lab[3]] == 0.0 and want["g_value"][0, lab[7]] == 0.0
     assert np.isnan(adv[0, lab[3] + 1].item())  # the advantages tensor itself is not sanitised, as in the reference
@@ -286,5 +295,11 @@ def test_native_step_with_a_value_head_equals_per_micro_batch_rl_step(libprl, cu
         assert abs(stats_a[k] - max(agg[k])) <= 1e-6 * max(1.0, abs(max(agg[k]))), k
     for k in ("min_advantage", "value_min"):
         assert abs(stats_a[k] - min(agg[k])) <= 1e-6 * max(1.0, abs(min(agg[k]))), k
+    # the summed value statistics by the size of their own terms: each micro-batch's fp32-rounded report is good to 2^-24 of itself
+    # (all of one sign for value_loss / value_mse; value_mean against the sum of the parts' magnitudes)
+    for k in ("value_mean", "value_loss", "value_mse"):
+        scale = sum(abs(v) for v in agg[k])
+        assert abs(stats_a[k] - sum(agg[k])) <= (vc.VALUE_STAT_BOUND + 2.0 ** -23) * scale, (k, stats_a[k], sum(agg[k]))
+    assert stats_a["value_max"] == max(agg["value_max"]) and stats_a["value_min"] == min(agg["value_min"])
     # the advantages the policy term used are rewards - V, not the column the preprocessor wrote
     assert abs(stats_a["advantage"] - sum(agg["advantage"])) <= FP_TOL and stats_a["value_loss"] > 0

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PRL_ABI_VERSION 15
+#define PRL_ABI_VERSION 16
 
 #define PRL_OK 0
 #define PRL_EINVAL (-22)   /* bad argument                                  */
@@ -627,6 +627,11 @@ int prl_bucket_scatter(const void* bucket, int64_t bucket_bytes, const struct pr
  * prl_optim_grad_norm writes norm_and_coef[0] = L2 norm over every segment with a gradient (fp64 sums in a
  *   fixed order: bitwise reproducible) and norm_and_coef[1] = min(1, max_norm / (norm + 1e-6)) formed in fp32
  *   as clip_grad_norm_ does (a non-finite norm propagates); max_norm <= 0 gives 1.
+ * prl_optim_grad_sumsq / prl_optim_clip_from_sumsq are its two halves, for a norm whose gradients are spread over
+ *   ranks (sharded optimizer state): the first leaves the fp64 sum of squares of the given segments in `*sumsq`
+ *   (device memory; the same per-chunk records folded in the same fixed order, no root, no clip; no live segment
+ *   gives 0), the caller adds the ranks' values, the second writes (float)sqrt(*sumsq) and the coefficient into the
+ *   record.  Back to back on one table they reproduce prl_optim_grad_norm's record bit for bit.
  * The step calls read the coefficient from `norm_and_coef` (NULL = 1). */
 typedef struct prl_optim_segment {
   void* param;
@@ -644,6 +649,9 @@ typedef struct prl_optim_segment {
 int prl_optim_workspace_bytes(int64_t n_segments, int64_t total_numel, size_t* bytes);
 int prl_optim_grad_norm(const prl_optim_segment* segments, int64_t n_segments, float max_norm, void* workspace,
                         size_t workspace_bytes, float* norm_and_coef, prl_stream_t stream);
+int prl_optim_grad_sumsq(const prl_optim_segment* segments, int64_t n_segments, void* workspace,
+                         size_t workspace_bytes, double* sumsq, prl_stream_t stream);
+int prl_optim_clip_from_sumsq(const double* sumsq, float max_norm, float* norm_and_coef, prl_stream_t stream);
 int prl_optim_adamw_step(const prl_optim_segment* segments, int64_t n_segments, double beta1, double beta2, double eps,
                          const float* norm_and_coef, prl_stream_t stream);
 int prl_optim_lion_step(const prl_optim_segment* segments, int64_t n_segments, double beta1, double beta2,

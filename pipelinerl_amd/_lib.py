@@ -13,7 +13,7 @@ from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libprl.so"
 
-PRL_ABI_VERSION = 15
+PRL_ABI_VERSION = 16
 PRL_OK = 0
 PRL_EINVAL = -22
 PRL_ENOMEM = -12
@@ -215,6 +215,8 @@ PROTOTYPES: dict[str, tuple] = {
     "prl_bucket_scatter": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "prl_optim_workspace_bytes": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
     "prl_optim_grad_norm": (c_int32, [_P, c_int64, c_float, _P, c_size_t, _P, _P]),
+    "prl_optim_grad_sumsq": (c_int32, [_P, c_int64, _P, c_size_t, _P, _P]),
+    "prl_optim_clip_from_sumsq": (c_int32, [_P, c_float, _P, _P]),
     "prl_optim_adamw_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
     "prl_optim_lion_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, _P, _P]),
     "prl_optim_grad_accumulate": (c_int32, [_P, c_int64, c_int32, _P]),

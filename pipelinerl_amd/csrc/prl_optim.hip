@@ -157,9 +157,8 @@ __global__ __launch_bounds__(kBlock) void grad_sumsq_kernel(const NormTable tab,
 
 // One workgroup folds the per-chunk records in a fixed order: thread t takes records t, t + 1024, ... into four
 // independent accumulators (the loads overlap), then the 1024 per-thread sums are added in index order by a tree.
-__global__ __launch_bounds__(kFinalBlock) void grad_norm_finalize_kernel(const double* __restrict__ partials, int64_t n, float max_norm,
-                                                                         float* __restrict__ norm_and_coef) {
-  __shared__ double lds[kFinalBlock];
+// Every thread returns; thread 0's value is the sum.
+__device__ __forceinline__ double fold_partials(const double* __restrict__ partials, int64_t n, double (&lds)[kFinalBlock]) {
   double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
   int64_t i = threadIdx.x;
   for (; i + 3 * kFinalBlock < n; i += 4 * kFinalBlock) {
@@ -175,11 +174,32 @@ __global__ __launch_bounds__(kFinalBlock) void grad_norm_finalize_kernel(const d
     if ((int)threadIdx.x < stride) lds[threadIdx.x] += lds[threadIdx.x + stride];
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    const float norm = (float)sqrt(lds[0]);
-    norm_and_coef[0] = norm;
-    norm_and_coef[1] = prl_clip_coef(norm, max_norm);
-  }
+  return lds[0];
+}
+
+__device__ __forceinline__ void write_norm_record(double sumsq, float max_norm, float* __restrict__ norm_and_coef) {
+  const float norm = (float)sqrt(sumsq);
+  norm_and_coef[0] = norm;
+  norm_and_coef[1] = prl_clip_coef(norm, max_norm);
+}
+
+__global__ __launch_bounds__(kFinalBlock) void grad_norm_finalize_kernel(const double* __restrict__ partials, int64_t n, float max_norm,
+                                                                         float* __restrict__ norm_and_coef) {
+  __shared__ double lds[kFinalBlock];
+  const double sumsq = fold_partials(partials, n, lds);
+  if (threadIdx.x == 0) write_norm_record(sumsq, max_norm, norm_and_coef);
+}
+
+// The two halves of the finalize for a norm that crosses ranks: the fold leaves the fp64 sum of squares of THIS rank's
+// segments on the device, the ranks add theirs, the record is formed from the total.
+__global__ __launch_bounds__(kFinalBlock) void grad_sumsq_fold_kernel(const double* __restrict__ partials, int64_t n, double* __restrict__ sumsq) {
+  __shared__ double lds[kFinalBlock];
+  const double t = fold_partials(partials, n, lds);
+  if (threadIdx.x == 0) *sumsq = t;
+}
+
+__global__ void clip_from_sumsq_kernel(const double* __restrict__ sumsq, float max_norm, float* __restrict__ norm_and_coef) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) write_norm_record(*sumsq, max_norm, norm_and_coef);
 }
 
 // ---- the step ---------------------------------------------------------------------------------------------------------
@@ -391,10 +411,9 @@ extern "C" int prl_optim_workspace_bytes(int64_t n_segments, int64_t total_numel
   return PRL_OK;
 }
 
-extern "C" int prl_optim_grad_norm(const prl_optim_segment* segments, int64_t n_segments, float max_norm, void* workspace,
-                                   size_t workspace_bytes, float* norm_and_coef, prl_stream_t stream) {
-  if (int rc = validate(segments, n_segments, false, false)) return rc;
-  PRL_CHECK_ARG(norm_and_coef != nullptr, "norm_and_coef is null");
+// (the caller has validated the table) one grad_sumsq_kernel launch per <= 64 live segments; *n_partials = number of per-chunk records written
+static int launch_partials(const prl_optim_segment* segments, int64_t n_segments, void* workspace, size_t workspace_bytes, hipStream_t s,
+                           int64_t* n_partials) {
   int64_t total_chunks = 0;
   for (int64_t i = 0; i < n_segments; ++i)
     if (live(segments[i])) total_chunks += chunks_of(segments[i].numel);
@@ -402,7 +421,6 @@ extern "C" int prl_optim_grad_norm(const prl_optim_segment* segments, int64_t n_
   PRL_CHECK_ARG(total_chunks == 0 || workspace != nullptr, "workspace is null");
   PRL_CHECK_ARG(workspace_bytes >= (size_t)total_chunks * sizeof(double), "workspace too small: %zu < %zu bytes for %lld chunks", workspace_bytes,
                 (size_t)total_chunks * sizeof(double), (long long)total_chunks);
-  hipStream_t s = static_cast<hipStream_t>(stream);
   double* partials = static_cast<double*>(workspace);
   int64_t i = 0, base = 0;
   while (i < n_segments) {
@@ -427,8 +445,39 @@ extern "C" int prl_optim_grad_norm(const prl_optim_segment* segments, int64_t n_
     PRL_LAUNCH_CHECK("grad_sumsq_kernel");
     base += chunks;
   }
-  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(kFinalBlock), 0, s, partials, base, max_norm, norm_and_coef);
+  *n_partials = base;
+  return PRL_OK;
+}
+
+extern "C" int prl_optim_grad_norm(const prl_optim_segment* segments, int64_t n_segments, float max_norm, void* workspace,
+                                   size_t workspace_bytes, float* norm_and_coef, prl_stream_t stream) {
+  if (int rc = validate(segments, n_segments, false, false)) return rc;
+  PRL_CHECK_ARG(norm_and_coef != nullptr, "norm_and_coef is null");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int64_t base = 0;
+  if (int rc = launch_partials(segments, n_segments, workspace, workspace_bytes, s, &base)) return rc;
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(kFinalBlock), 0, s, static_cast<const double*>(workspace), base, max_norm, norm_and_coef);
   PRL_LAUNCH_CHECK("grad_norm_finalize_kernel");
+  return PRL_OK;
+}
+
+extern "C" int prl_optim_grad_sumsq(const prl_optim_segment* segments, int64_t n_segments, void* workspace, size_t workspace_bytes,
+                                    double* sumsq, prl_stream_t stream) {
+  if (int rc = validate(segments, n_segments, false, false)) return rc;
+  PRL_CHECK_ARG(sumsq != nullptr, "sumsq is null");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int64_t base = 0;
+  if (int rc = launch_partials(segments, n_segments, workspace, workspace_bytes, s, &base)) return rc;
+  hipLaunchKernelGGL(grad_sumsq_fold_kernel, dim3(1), dim3(kFinalBlock), 0, s, static_cast<const double*>(workspace), base, sumsq);  // no segment: writes 0
+  PRL_LAUNCH_CHECK("grad_sumsq_fold_kernel");
+  return PRL_OK;
+}
+
+extern "C" int prl_optim_clip_from_sumsq(const double* sumsq, float max_norm, float* norm_and_coef, prl_stream_t stream) {
+  PRL_CHECK_ARG(sumsq != nullptr, "sumsq is null");
+  PRL_CHECK_ARG(norm_and_coef != nullptr, "norm_and_coef is null");
+  hipLaunchKernelGGL(clip_from_sumsq_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), sumsq, max_norm, norm_and_coef);
+  PRL_LAUNCH_CHECK("clip_from_sumsq_kernel");
   return PRL_OK;
 }
 

@@ -18,7 +18,27 @@ write `state[p]["master"]` (or drop the state), otherwise the next step writes t
 parameter's storage (`ColocatedSender.rehome`) is fine: the values travel, and the new address is picked up.
 
 Data parallelism: gradients are already reduced when the accumulation boundary is reached (DDP averages them in backward), so
-the norm computed here is complete on every rank.  ZeRO / FSDP sharded norms are out of scope.
+the norm computed here is complete on every rank.
+
+Sharded state (ZeRO-1; `shard_group=` a torch.distributed group, or `shard=(rank, world)` without one): the parameters, in
+`param_groups` order and each padded to a 16-element slot, form one element space that is cut into `world` equal ranges of
+`shard_len` elements (a multiple of 16): `plan_shards`.  A rank allocates `exp_avg`, `exp_avg_sq`, `master` and `step` for its
+range only (three flat buffers of `shard_len` floats) and steps the pieces of the parameters inside it - ordinary segments of the
+same kernels whose pointers are offset by a multiple of 16 elements, so the 16-byte vector path is kept.  The method names and
+their order at the boundary do not change; the collectives happen inside them:
+  * `grad_accum_dtype=None`: `p.grad` is complete on every rank (DDP), the norm is the unsharded one; only the step is restricted.
+  * `grad_accum_dtype=torch.float32`: every parameter (fp32 ones too) has a slot in a flat accumulator laid out like the element
+    space; `reduce_accumulated` reduces it to the owners (`reduce_scatter_tensor` over RCCL, `all_reduce` over gloo - the choice
+    follows the backend only) and divides the own range by the world size.  No rank then holds every reduced gradient:
+    `compute_grad_norm` sums the squares of the own pieces (`prl_optim_grad_sumsq`), adds the ranks' fp64 values with one
+    `all_reduce`, and forms norm and coefficient from the total on the device (`prl_optim_clip_from_sumsq`).
+  * `step()` updates the own pieces where the parameters live, packs them into a send buffer (`prl_bucket_gather`; the parameter's
+    own dtype, 16-byte aligned pieces, padded to the largest rank's size), exchanges the buffers (`all_gather_into_tensor` /
+    `all_gather`) and writes the other ranks' pieces into the parameters (`prl_bucket_scatter`).  Buffers are allocated once.
+With `shard=` there is no group to call: the caller moves the data between the halves that the methods above are made of
+(`prepare_reduce` / `finish_reduce`, `local_grad_sumsq` / `norm_from_sumsq`, `pack_shard` / `unpack_shards`) - one process can
+stand in for every rank.  `state_dict()` is this rank's shard plus the partition; `full_state_dict()` gathers an unsharded
+dictionary on rank 0, and an unsharded dictionary loads into shards (each rank takes its ranges).
 
 Gradient accumulation (`grad_accum_dtype=torch.float32`): autograd sums the micro-batch gradients into `p.grad` in the
 parameter's dtype, and a bf16 running sum drops every term below half an ulp of it - after 256 equal terms all of the next one.
@@ -56,6 +76,79 @@ def get_grouped_params(model: torch.nn.Module, weight_decay: float, no_decay: li
     return [{"params": groups[0], "weight_decay": weight_decay}, {"params": groups[1], "weight_decay": 0.0}]
 
 
+def shard_layout(numels, world: int, slot: int = _SLOT) -> tuple[list[int], int]:
+    """(offset of every parameter in the slot-padded element space, shard_len): the padded length rounded up to `world` ranges of
+    a multiple of `slot` elements."""
+    if world < 1 or slot < 1:
+        raise ValueError(f"plan_shards: world ({world}) and slot ({slot}) must be positive")
+    offsets, off = [], 0
+    for n in numels:
+        offsets.append(off)
+        off += -(-int(n) // slot) * slot
+    return offsets, -(-off // (world * slot)) * slot
+
+
+def plan_shards(numels, world: int, slot: int = _SLOT) -> list[list[tuple[int, int, int]]]:
+    """The partition of sharded optimizer state: per rank the list of `(param_index, begin, end)` element ranges it owns.
+    Rank r owns `[r shard_len, (r + 1) shard_len)` of the padded space, so every `begin` is a multiple of `slot` inside its
+    parameter and only a piece's length can be ragged.  A world larger than the slot count leaves the last ranks empty."""
+    offsets, shard_len = shard_layout(numels, world, slot)
+    plan = []
+    for r in range(world):
+        lo, hi = r * shard_len, (r + 1) * shard_len
+        pieces = []
+        for i, (off, n) in enumerate(zip(offsets, numels)):
+            b, e = max(off, lo) - off, min(off + int(n), hi) - off
+            if e > b:
+                pieces.append((i, b, e))
+        plan.append(pieces)
+    return plan
+
+
+def _resolve_shard(shard_group, shard) -> tuple[int, int] | None:
+    """(rank, world) of the sharded state, None for a world of one (today's unsharded behaviour)."""
+    if shard_group is not None and shard is not None:
+        raise ValueError("fused optimizer: give shard_group= (a torch.distributed group) or shard=(rank, world), not both")
+    if shard is not None:
+        rank, world = int(shard[0]), int(shard[1])
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"fused optimizer: shard=(rank, world): rank {rank} is not in [0, {world})")
+    elif shard_group is not None:
+        import torch.distributed as dist
+
+        rank, world = dist.get_rank(shard_group), dist.get_world_size(shard_group)
+    else:
+        return None
+    return (rank, world) if world > 1 else None
+
+
+def merge_shard_state_dicts(shards: list[dict]) -> dict:
+    """The unsharded state dictionary of the `state_dict()`s of every rank of one sharded optimizer."""
+    shards = sorted(shards, key=lambda d: d["shard"]["rank"])
+    meta = shards[0]["shard"]
+    if [d["shard"]["rank"] for d in shards] != list(range(meta["world"])):
+        raise ValueError(f"merge_shard_state_dicts: need the shard of every rank of a world of {meta['world']}, got ranks {[d['shard']['rank'] for d in shards]}")
+    state: dict[int, dict] = {}
+    for d in shards:
+        for pid, st in d["state"].items():
+            b, e = d["shard"]["ranges"][pid]
+            full = state.setdefault(pid, {})
+            for k, v in st.items():
+                if k == "step":
+                    full[k] = torch.as_tensor(v, dtype=torch.float32).detach().cpu().clone()
+                    continue
+                if k not in full:
+                    full[k] = torch.zeros(meta["numels"][pid], dtype=torch.float32, device=v.device)
+                full[k][b:e] = v.reshape(-1)
+    for pid, st in state.items():
+        for k in st:
+            if k != "step":
+                st[k] = st[k].view(meta["shapes"][pid])
+    import copy
+
+    return {"state": state, "param_groups": copy.deepcopy(shards[0]["param_groups"])}
+
+
 def _check_hyper(lr: float, betas: tuple[float, float], weight_decay: float, eps: float = 0.0) -> None:
     if not 0.0 <= lr:
         raise ValueError(f"Invalid learning rate: {lr}")
@@ -74,10 +167,21 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     _state_keys: tuple[str, ...] = ("exp_avg",)
 
-    def __init__(self, params: Iterable, defaults: dict[str, Any], master_weights: bool, grad_accum_dtype: torch.dtype | None = None):
+    def __init__(self, params: Iterable, defaults: dict[str, Any], master_weights: bool, grad_accum_dtype: torch.dtype | None = None,
+                 shard_group=None, shard: tuple[int, int] | None = None):
         if grad_accum_dtype not in (None, torch.float32):
             raise ValueError(f"fused optimizer: grad_accum_dtype must be None or torch.float32 (got {grad_accum_dtype})")
+        self._shard = _resolve_shard(shard_group, shard)  # (rank, world), world > 1; None: unsharded
+        self._shard_group = shard_group if self._shard is not None else None
         super().__init__(params, defaults)
+        self._lay = None                          # sharded: (numels, params, offsets, shard_len, {param index: (begin, end)})
+        self._shard_flat: dict[str, torch.Tensor] = {}  # sharded: state key -> flat buffer of shard_len floats
+        self._reduced = False                     # sharded fp32 accumulation: the own range holds the averaged gradients
+        self._sumsq: torch.Tensor | None = None   # sharded: device fp64, the sum of squares of the own pieces
+        self._norm_table = None                   # sharded, complete p.grad: every gradient whole, for the norm
+        self._pub = None                          # sharded: send / receive buffers and the piece layout of the weight exchange
+        self._pub_tables = None
+        self._device: torch.device | None = None
         self.master_weights = bool(master_weights)
         self.grad_accum_dtype = grad_accum_dtype
         self._acc_flat: torch.Tensor | None = None      # the flat fp32 accumulator buffer (slot-padded like the state)
@@ -103,6 +207,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     def _ensure_state(self) -> None:
         """State of every parameter that has a gradient and none yet (or a loaded one that is not in a flat buffer)."""
+        if self._shard is not None:
+            return self._ensure_state_sharded()
         for group in self.param_groups:
             todo = []
             for p in group["params"]:
@@ -137,6 +243,85 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 self.state[p].setdefault("step", torch.tensor(0.0, dtype=torch.float32))
         self._flat = [f for f in self._flat if any(self._owns(f, st) for st in self.state.values())]
 
+    # ---- sharded state --------------------------------------------------------------------------------------------------
+    def _layout(self):
+        params = [p for group in self.param_groups for p in group["params"]]
+        numels = tuple(p.numel() for p in params)
+        if self._lay is None or self._lay[0] != numels:
+            if self._lay is not None and (self._shard_flat or self._acc_flat is not None):
+                raise RuntimeError("fused optimizer: the parameter list changed after the sharded state was allocated; the partition is fixed by then")
+            rank, world = self._shard
+            offsets, shard_len = shard_layout(numels, world)
+            mine = {i: (b, e) for i, b, e in plan_shards(numels, world)[rank]}
+            if rank == 0:  # a parameter without elements has no piece; its step count lives on rank 0, so that the gathered state is complete
+                mine.update({i: (0, 0) for i, n in enumerate(numels) if n == 0})
+            self._lay = (numels, params, offsets, shard_len, mine)
+            self._pub = self._pub_tables = None
+        return self._lay
+
+    @property
+    def shard_len(self) -> int | None:
+        """Elements of the padded parameter space this rank owns (None: unsharded)."""
+        return None if self._shard is None else self._layout()[3]
+
+    def _ensure_state_sharded(self) -> None:
+        """The flat buffers hold this rank's range only; an owned piece gets its views once its parameter has a gradient."""
+        _, params, offsets, shard_len, mine = self._layout()
+        if not params:
+            return
+        device = params[0].device
+        if not self._shard_flat:
+            keys = self._state_keys + (("master",) if any(self._wants_master(p) for p in params) else ())
+            self._shard_flat = {k: torch.zeros(shard_len, dtype=torch.float32, device=device) for k in keys}
+            self._flat = list(self._shard_flat.values())
+        lo = self._shard[0] * shard_len
+        for i, p in enumerate(params):
+            if i not in mine or self._grad_of(p) is None:
+                continue
+            b, e = mine[i]
+            st = self.state[p]
+            for k in self._keys_of(p):
+                view = self._shard_flat[k][offsets[i] + b - lo:offsets[i] + e - lo]
+                cur = st.get(k)
+                if cur is not None and cur.data_ptr() == view.data_ptr() and cur.numel() == view.numel() and self._is_flat_view(cur):
+                    continue
+                if cur is not None:  # loaded from a checkpoint: keep its values
+                    if cur.numel() != e - b:
+                        raise ValueError(f"fused optimizer: loaded state '{k}' of parameter {i} has {cur.numel()} elements, its piece [{b}, {e}) has {e - b}")
+                    view.copy_(cur.to(device=device, dtype=torch.float32).reshape(-1))
+                elif k == "master":
+                    view.copy_(p.detach().reshape(-1)[b:e])
+                st[k] = view
+            st.setdefault("step", torch.tensor(0.0, dtype=torch.float32))
+
+    def state_dict(self) -> dict:
+        """Unsharded: torch's.  Sharded: this rank's pieces (1-D) under torch's keys, plus `"shard"`: the partition."""
+        d = super().state_dict()
+        if self._shard is not None:
+            numels, params, _, shard_len, mine = self._layout()
+            d["shard"] = {"world": self._shard[1], "rank": self._shard[0], "slot": _SLOT, "total_slots": self._shard[1] * shard_len // _SLOT,
+                          "shard_len": shard_len, "numels": list(numels), "shapes": [tuple(p.shape) for p in params],
+                          "ranges": {i: be for i, be in mine.items()}}
+        return d
+
+    def full_state_dict(self, group=None) -> dict | None:
+        """The unsharded dictionary on rank 0 of the group (None elsewhere): every rank's shard travels through the host
+        (`gather_object`) - a checkpoint path, not a step path.  An unsharded optimizer loads it and continues identically.
+        With `shard=` there is no group: collect every stand-in's `state_dict()` and call `merge_shard_state_dicts`."""
+        d = self.state_dict()
+        if self._shard is None:
+            return d
+        import torch.distributed as dist
+
+        group = self._shard_group if group is None else group
+        if group is None:
+            raise RuntimeError("fused optimizer: full_state_dict() needs the group (shard=: use merge_shard_state_dicts on every rank's state_dict())")
+        d["state"] = {pid: {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in st.items()} for pid, st in d["state"].items()}
+        rank, world = self._shard
+        gathered = [None] * world if rank == 0 else None
+        dist.gather_object(d, gathered, dst=dist.get_global_rank(group, 0), group=group)
+        return merge_shard_state_dicts(gathered) if rank == 0 else None
+
     @staticmethod
     def _owns(flat: torch.Tensor, st: dict) -> bool:
         ptr = flat.untyped_storage().data_ptr()
@@ -144,7 +329,15 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict: dict) -> None:
         """torch casts loaded state to the parameter's dtype; the state here is fp32 whatever the parameter is, so the saved
-        tensors are taken as they are (a torch.optim.AdamW checkpoint of fp32 parameters loads: same keys)."""
+        tensors are taken as they are (a torch.optim.AdamW checkpoint of fp32 parameters loads: same keys).
+        Sharded: a shard dictionary of the same world and rank, or an unsharded one from which this rank takes its ranges."""
+        saved = state_dict.get("shard")
+        here = self._shard or (0, 1)
+        if saved is not None and (saved["rank"], saved["world"]) != here:
+            raise ValueError(f"fused optimizer: this state was saved by rank {saved['rank']} of a world of {saved['world']} and cannot be loaded into "
+                             f"rank {here[0]} of a world of {here[1]}; gather it with full_state_dict() and load the unsharded dictionary")
+        if self._shard is not None:
+            return self._load_state_dict_sharded(state_dict, saved is not None)
         super().load_state_dict(state_dict)
         saved_ids = [i for g in state_dict["param_groups"] for i in g["params"]]
         ours = [p for g in self.param_groups for p in g["params"]]
@@ -159,6 +352,24 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 self.state[p]["step"] = torch.as_tensor(src["step"], dtype=torch.float32).detach().cpu().clone()
         self._flat, self._table, self._table_key = [], None, []
 
+    def _load_state_dict_sharded(self, state_dict: dict, pieces: bool) -> None:
+        """Hyper-parameters through torch; of the state only the own ranges are brought to the device."""
+        super().load_state_dict({"state": {}, "param_groups": state_dict["param_groups"]})
+        saved_ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        _, params, _, _, mine = self._layout()
+        for i, (pid, p) in enumerate(zip(saved_ids, params)):
+            src = state_dict["state"].get(pid)
+            if src is None or i not in mine:
+                continue
+            b, e = mine[i]
+            for k in self._state_keys + ("master",):
+                if k in src:
+                    t = src[k].detach().reshape(-1)
+                    self.state[p][k] = (t if pieces else t[b:e]).to(device=p.device, dtype=torch.float32).clone()
+            if "step" in src:
+                self.state[p]["step"] = torch.as_tensor(src["step"], dtype=torch.float32).detach().cpu().clone()
+        self._shard_flat, self._flat, self._table, self._table_key = {}, [], None, []
+
     # ---- fp32 gradient accumulation ---------------------------------------------------------------------------------------
     def _grad_of(self, p: torch.Tensor) -> torch.Tensor | None:
         """What norm and step read for `p`: its accumulator once something was folded into it, else `p.grad`."""
@@ -171,9 +382,13 @@ class _FusedOptimizer(torch.optim.Optimizer):
         """The static rule (the same on every rank): a parameter whose gradient dtype is not fp32 has an accumulator."""
         return (getattr(p, "grad_dtype", None) or p.dtype) != torch.float32
 
+    def _has_slot(self, p: torch.Tensor) -> bool:
+        """Sharded: every parameter has an accumulator slot (the flat buffer is what the ranks reduce), fp32 gradients included."""
+        return self._shard is not None or self._accumulates(p)
+
     def _unfolded(self, p: torch.Tensor) -> bool:
         g = p.grad
-        if g is None or g.dtype == torch.float32:
+        if g is None or (g.dtype == torch.float32 and self._shard is None):
             return False
         z = self._acc_zeroed.get(p)
         return not (z is not None and z[0] is g and z[1] == g._version)  # zeroed in place by the last fold and untouched since
@@ -188,6 +403,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     def _ensure_accumulators(self, extra: Iterable[torch.Tensor] = ()) -> None:
         """One flat fp32 buffer with a 64-byte aligned slot per accumulating parameter; rebuilt (filled slots copied) when a parameter joins."""
+        if self._shard is not None:
+            return self._ensure_accumulators_sharded()
         owners = [p for group in self.param_groups for p in group["params"] if self._accumulates(p) or p in self._acc]
         have = {id(p) for p in owners}
         owners += [p for p in extra if id(p) not in have]
@@ -207,6 +424,20 @@ class _FusedOptimizer(torch.optim.Optimizer):
             if p in self._acc_filled:
                 views[p].copy_(self._acc[p])
         self._acc_flat, self._acc = flat, views
+
+    def _ensure_accumulators_sharded(self) -> None:
+        """One flat fp32 buffer over the whole padded parameter space (world x shard_len): what the ranks reduce to its owners."""
+        if self._acc_flat is not None:
+            self._layout()  # (raises when the parameter list changed)
+            return
+        _, params, offsets, shard_len, _ = self._layout()
+        if not params:
+            return
+        devices = {p.device for p in params}
+        if len(devices) > 1:
+            raise ValueError(f"fused optimizer: all parameters must live on one device (got {sorted(map(str, devices))})")
+        flat = torch.zeros(self._shard[1] * shard_len, dtype=torch.float32, device=params[0].device)
+        self._acc_flat, self._acc = flat, {p: flat[off:off + p.numel()].view(p.shape) for p, off in zip(params, offsets)}
 
     @torch.no_grad()
     def accumulate_grads(self, set_to_none: bool = True) -> None:
@@ -250,6 +481,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
         if self.grad_accum_dtype is None:
             raise RuntimeError("fused optimizer: reduce_accumulated() needs grad_accum_dtype=torch.float32")
+        if self._shard is not None:
+            return self._reduce_accumulated_sharded(group)
         if not (dist.is_available() and dist.is_initialized()):
             return
         world = dist.get_world_size(group)
@@ -273,11 +506,56 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 dist.all_reduce(p.grad, op=dist.ReduceOp.SUM, group=group)
                 p.grad.div_(world)
 
+    def _reduce_accumulated_sharded(self, group=None) -> None:
+        """Reduce the flat accumulator to its owners and average the own range.  RCCL: `reduce_scatter_tensor` in place (the output
+        is the own range of the input, the in-place form of the collective); gloo has no reduce-scatter: `all_reduce`."""
+        import torch.distributed as dist
+
+        if self._shard_group is None:
+            raise RuntimeError("fused optimizer: shard= has no group to reduce over; move the data between prepare_reduce() and finish_reduce()")
+        group = self._shard_group
+        if dist.get_world_size(group) != self._shard[1]:
+            raise RuntimeError(f"fused optimizer: the state is sharded over {self._shard[1]} ranks, the group has {dist.get_world_size(group)}")
+        flat = self.prepare_reduce()
+        if dist.get_backend(group) == "nccl":
+            rank, shard_len = self._shard[0], self._layout()[3]
+            dist.reduce_scatter_tensor(flat[rank * shard_len:(rank + 1) * shard_len], flat, op=dist.ReduceOp.SUM, group=group)
+        else:
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+        self.finish_reduce()
+
+    @torch.no_grad()
+    def prepare_reduce(self) -> torch.Tensor:
+        """Sharded fp32 accumulation, first half of `reduce_accumulated`: the flat accumulator (world x shard_len floats) with every
+        slot that received nothing zeroed, ready to be summed over the ranks."""
+        if self._shard is None or self.grad_accum_dtype is None:
+            raise RuntimeError("fused optimizer: prepare_reduce() belongs to sharded state with grad_accum_dtype=torch.float32")
+        self._check_all_folded()
+        self._ensure_accumulators()
+        for p, view in self._acc.items():
+            if p not in self._acc_filled:
+                view.zero_()
+        return self._acc_flat
+
+    @torch.no_grad()
+    def finish_reduce(self, owned: torch.Tensor | None = None) -> None:
+        """Second half: `owned` = the sum over the ranks of this rank's range (None: it already stands in the accumulator); the
+        range is divided by the world size and every slot counts as having a gradient, so the ranks take identical steps."""
+        rank, world = self._shard
+        shard_len = self._layout()[3]
+        mine = self._acc_flat[rank * shard_len:(rank + 1) * shard_len]
+        if owned is not None:
+            mine.copy_(owned)
+        mine.div_(world)
+        self._acc_filled.update(self._acc)
+        self._reduced = True
+
     def zero_grad(self, set_to_none: bool = True) -> None:
         """Clears `p.grad` as torch does and marks every accumulator empty (no memset: the next fold overwrites)."""
         super().zero_grad(set_to_none=set_to_none)
         self._acc_filled.clear()
         self._acc_zeroed.clear()
+        self._reduced = False
 
     # ---- segment table ----------------------------------------------------------------------------------------------------
     def _check_tensor(self, p: torch.Tensor, g: torch.Tensor | None) -> None:
@@ -296,21 +574,39 @@ class _FusedOptimizer(torch.optim.Optimizer):
         if len(devices) > 1:
             raise ValueError(f"fused optimizer: all parameters must live on one device (got {sorted(map(str, devices))})")
         self._ensure_state()
+        everything = entries
+        if self._shard is not None:  # one segment per owned piece; `entries` = the parameters this rank owns a piece of
+            mine = self._layout()[4]
+            ranges = [mine[i] for i in range(len(everything)) if i in mine]
+            entries = [e for i, e in enumerate(everything) if i in mine]
+        else:
+            ranges = [(0, p.numel()) for p, _ in entries]
         table = (_lib.PrlOptimSegment * max(len(entries), 1))()
-        for seg, (p, _) in zip(table, entries):
+        for seg, (p, _), (b, e) in zip(table, entries, ranges):
             g = self._grad_of(p)
             st = self.state[p] if g is not None else {}
-            seg.param, seg.numel, seg.param_dtype = p.data_ptr(), p.numel(), _DTYPES[p.dtype]
-            seg.grad = g.data_ptr() if g is not None and p.numel() else None
+            seg.param, seg.numel, seg.param_dtype = p.data_ptr() + b * p.element_size(), e - b, _DTYPES[p.dtype]
+            seg.grad = g.data_ptr() + b * g.element_size() if g is not None and p.numel() else None
             seg.grad_dtype = _DTYPES[g.dtype] if g is not None else _DTYPES[p.dtype]
             if g is not None:
                 seg.exp_avg = st["exp_avg"].data_ptr()
                 seg.exp_avg_sq = st["exp_avg_sq"].data_ptr() if "exp_avg_sq" in st else None
                 seg.master = st["master"].data_ptr() if "master" in st else None
+        self._norm_table = None
+        if self._shard is not None and self.grad_accum_dtype is None:  # complete gradients on every rank: the norm reads them whole
+            self._norm_table = (_lib.PrlOptimSegment * max(len(everything), 1))()
+            for seg, (p, _) in zip(self._norm_table, everything):
+                g = p.grad
+                seg.numel, seg.param_dtype = p.numel(), _DTYPES[p.dtype]
+                seg.grad = g.data_ptr() if g is not None and p.numel() else None
+                seg.grad_dtype = _DTYPES[g.dtype] if g is not None else _DTYPES[p.dtype]
         self._table, self._table_params = table, entries
-        self._table_key = self._key(entries)
+        owned = {id(p) for p, _ in entries}
+        self._table_group_sizes = [sum(id(p) in owned for p in group["params"]) for group in self.param_groups]
+        self._table_key, self._table_n_all = self._key(everything), len(everything)
+        entries = everything
         if entries:
-            device = entries[0][0].device
+            device = self._device = entries[0][0].device
             if self._record is None:
                 self._record = torch.zeros(2, dtype=torch.float32, device=device)
             need = ctypes.c_size_t(0)  # re-queried on every rebuild: add_param_group may have added elements
@@ -324,12 +620,12 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     def _current_table(self):
         entries = [(p, group) for group in self.param_groups for p in group["params"]]
-        if self._table is None or len(entries) != len(self._table_params) or self._key(entries) != self._table_key:
+        if self._table is None or len(entries) != self._table_n_all or self._key(entries) != self._table_key:
             self._build_table()
         return self._table, self._table_params
 
     def _stream(self) -> int:
-        return _lib.current_stream_ptr(self._table_params[0][0].device)
+        return _lib.current_stream_ptr(self._device)
 
     # ---- the public steps ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -340,11 +636,53 @@ class _FusedOptimizer(torch.optim.Optimizer):
         `max_norm` None or <= 0 reports the norm and clips nothing."""
         lib = _lib.load()
         self._check_all_folded()
+        if self._shard is not None and self.grad_accum_dtype is not None:
+            # no rank holds every reduced gradient: shard partials, one fp64 all_reduce, the record from the total - stream-ordered
+            if self._shard_group is None:
+                raise RuntimeError("fused optimizer: shard= has no group to add the partial sums over; use local_grad_sumsq() and norm_from_sumsq()")
+            import torch.distributed as dist
+
+            sumsq = self.local_grad_sumsq()
+            dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self._shard_group)
+            return self.norm_from_sumsq(sumsq, max_norm)
         table, entries = self._current_table()
-        if not entries:
+        if not self._table_n_all:
             raise ValueError("fused optimizer: no parameters")
+        if self._norm_table is not None:
+            table, entries = self._norm_table, range(self._table_n_all)
         _lib.check(lib.prl_optim_grad_norm(table, len(entries), 0.0 if max_norm is None else float(max_norm), self._workspace.data_ptr(),
                                            self._workspace.numel(), self._record.data_ptr(), self._stream()))
+        return self._record[0].clone()
+
+    def _check_reduced(self) -> None:
+        if self._shard is not None and self.grad_accum_dtype is not None and not self._reduced:
+            raise RuntimeError("fused optimizer: the sharded accumulators were not reduced since the last step; call reduce_accumulated() first")
+
+    @torch.no_grad()
+    def local_grad_sumsq(self) -> torch.Tensor:
+        """Sharded fp32 accumulation: the fp64 sum of squares of the reduced gradients of this rank's pieces, on the device
+        (a 1-element tensor that the next call overwrites).  The ranks' values are added, then `norm_from_sumsq`."""
+        if self._shard is None or self.grad_accum_dtype is None:
+            raise RuntimeError("fused optimizer: local_grad_sumsq() belongs to sharded state with grad_accum_dtype=torch.float32")
+        self._check_all_folded()
+        self._check_reduced()
+        table, entries = self._current_table()
+        if not self._table_n_all:
+            raise ValueError("fused optimizer: no parameters")
+        if self._sumsq is None:
+            self._sumsq = torch.zeros(1, dtype=torch.float64, device=self._device)
+        _lib.check(_lib.load().prl_optim_grad_sumsq(table, len(entries), self._workspace.data_ptr(), self._workspace.numel(), self._sumsq.data_ptr(),
+                                                    self._stream()))
+        return self._sumsq
+
+    @torch.no_grad()
+    def norm_from_sumsq(self, sumsq: torch.Tensor, max_norm: float | None) -> torch.Tensor:
+        """Norm and clip coefficient from the sum of squares over ALL ranks (device, fp64) into the record `step(clipped=True)` reads."""
+        if sumsq.dtype != torch.float64 or not sumsq.is_cuda or sumsq.numel() != 1:
+            raise ValueError("fused optimizer: norm_from_sumsq() takes one float64 value on the device")
+        self._current_table()
+        _lib.check(_lib.load().prl_optim_clip_from_sumsq(sumsq.data_ptr(), 0.0 if max_norm is None else float(max_norm), self._record.data_ptr(),
+                                                         self._stream()))
         return self._record[0].clone()
 
     def clip_and_step(self, max_norm: float | None) -> torch.Tensor:
@@ -363,8 +701,9 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 loss = closure()
         lib = _lib.load()
         self._check_all_folded()
+        self._check_reduced()
         table, entries = self._current_table()
-        if not entries:
+        if not self._table_n_all:
             return loss
         for seg, (p, group) in zip(table, entries):
             if self._grad_of(p) is None:
@@ -375,11 +714,82 @@ class _FusedOptimizer(torch.optim.Optimizer):
             seg.lr, seg.weight_decay = float(group["lr"]), float(group["weight_decay"])
         self._launch(lib, table, len(entries), self._record.data_ptr() if clipped else None)
         self._acc_filled.clear()  # the next fold of every accumulator overwrites
+        self._reduced = False
+        if self._shard_group is not None:
+            self._exchange_weights()
         return loss
+
+    # ---- sharded: publishing the updated pieces ---------------------------------------------------------------------------
+    def _publish_buffers(self):
+        """Byte layout of every rank's send buffer (the same on every rank): its pieces in plan order, each at a 16-byte aligned
+        offset, the buffer padded to the largest rank's size.  Allocated once."""
+        if self._pub is None:
+            numels, params, _, _, _ = self._layout()
+            per_rank, size = [], 0
+            for pieces in plan_shards(numels, self._shard[1]):
+                off, segs = 0, []
+                for i, b, e in pieces:
+                    isz = params[i].element_size()
+                    segs.append((i, b * isz, (e - b) * isz, off))
+                    off += -(-(e - b) * isz // 16) * 16
+                per_rank.append(segs)
+                size = max(size, off)
+            size = max(size, 16)
+            device = params[0].device
+            self._pub = (per_rank, size, torch.zeros(size, dtype=torch.uint8, device=device), torch.zeros(self._shard[1] * size, dtype=torch.uint8, device=device))
+        return self._pub
+
+    def _publish_tables(self):
+        """`prl_segment` tables of the exchange: own pieces -> send buffer, the other ranks' pieces <- receive buffer; rebuilt when a
+        parameter moved."""
+        per_rank, size, _, _ = self._publish_buffers()
+        params = self._layout()[1]
+        key = [p.data_ptr() for p in params]
+        if self._pub_tables is None or self._pub_tables[0] != key:
+            rank = self._shard[0]
+            out = (_lib.PrlSegment * max(len(per_rank[rank]), 1))()
+            for seg, (i, at, nbytes, off) in zip(out, per_rank[rank]):
+                seg.tensor, seg.bucket_offset, seg.nbytes = params[i].data_ptr() + at, off, nbytes
+            others = [(r, piece) for r, pieces in enumerate(per_rank) if r != rank for piece in pieces]
+            inn = (_lib.PrlSegment * max(len(others), 1))()
+            for seg, (r, (i, at, nbytes, off)) in zip(inn, others):
+                seg.tensor, seg.bucket_offset, seg.nbytes = params[i].data_ptr() + at, r * size + off, nbytes
+            self._pub_tables = (key, out, len(per_rank[rank]), inn, len(others))
+        return self._pub_tables
+
+    @torch.no_grad()
+    def pack_shard(self) -> torch.Tensor:
+        """This rank's pieces of the parameters, as they stand, packed into its send buffer (uint8, the same size on every rank)."""
+        _, size, send, _ = self._publish_buffers()
+        _, out, n_out, _, _ = self._publish_tables()
+        _lib.check(_lib.load().prl_bucket_gather(send.data_ptr(), size, out, n_out, _lib.current_stream_ptr(send.device)))
+        return send
+
+    @torch.no_grad()
+    def unpack_shards(self, gathered: torch.Tensor) -> None:
+        """`gathered`: every rank's send buffer in rank order (world x size bytes); the other ranks' pieces are written into the
+        parameters, the own ones are already there."""
+        _, size, _, _ = self._publish_buffers()
+        _, _, _, inn, n_in = self._publish_tables()
+        if gathered.dtype != torch.uint8 or gathered.numel() != self._shard[1] * size or not gathered.is_contiguous():
+            raise ValueError(f"fused optimizer: unpack_shards() takes {self._shard[1]} x {size} contiguous bytes")
+        _lib.require_device(gathered)
+        _lib.check(_lib.load().prl_bucket_scatter(gathered.data_ptr(), gathered.numel(), inn, n_in, _lib.current_stream_ptr(gathered.device)))
+
+    def _exchange_weights(self) -> None:
+        import torch.distributed as dist
+
+        _, _, _, recv = self._publish_buffers()
+        send = self.pack_shard()
+        if dist.get_backend(self._shard_group) == "nccl":
+            dist.all_gather_into_tensor(recv, send, group=self._shard_group)
+        else:
+            dist.all_gather(list(recv.view(self._shard[1], -1).unbind(0)), send, group=self._shard_group)
+        self.unpack_shards(recv)
 
     def _launch(self, lib, table, n: int, record: int | None) -> None:
         """One call per run of consecutive groups that agree on the launch-level constants (betas, eps): normally one."""
-        sizes = [len(g["params"]) for g in self.param_groups]
+        sizes = self._table_group_sizes  # the table's entries per group (sharded: the parameters this rank owns a piece of)
         keys = [self._launch_key(g) for g in self.param_groups]
         first, off = 0, 0
         for i in range(len(sizes)):
@@ -405,9 +815,9 @@ class FusedAdamW(_FusedOptimizer):
     _state_keys = ("exp_avg", "exp_avg_sq")
 
     def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 master_weights: bool = True, grad_accum_dtype: torch.dtype | None = None):
+                 master_weights: bool = True, grad_accum_dtype: torch.dtype | None = None, shard_group=None, shard: tuple[int, int] | None = None):
         _check_hyper(lr, betas, weight_decay, eps)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), master_weights, grad_accum_dtype)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), master_weights, grad_accum_dtype, shard_group, shard)
 
     def _launch_key(self, group):
         return (float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]))
@@ -422,9 +832,9 @@ class FusedLion(_FusedOptimizer):
     _state_keys = ("exp_avg",)
 
     def __init__(self, params, lr: float = 1e-4, betas: tuple[float, float] = (0.9, 0.99), weight_decay: float = 0.0, master_weights: bool = True,
-                 grad_accum_dtype: torch.dtype | None = None):
+                 grad_accum_dtype: torch.dtype | None = None, shard_group=None, shard: tuple[int, int] | None = None):
         _check_hyper(lr, betas, weight_decay)
-        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay), master_weights, grad_accum_dtype)
+        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay), master_weights, grad_accum_dtype, shard_group, shard)
 
     def _launch_key(self, group):
         return (float(group["betas"][0]), float(group["betas"][1]))
@@ -433,14 +843,18 @@ class FusedLion(_FusedOptimizer):
         _lib.check(lib.prl_optim_lion_step(table, n, key[0], key[1], record, self._stream()))
 
 
-def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weight_decay: float, grad_accum_dtype: torch.dtype | None = None):
+def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weight_decay: float, grad_accum_dtype: torch.dtype | None = None,
+                  shard_group=None, shard: tuple[int, int] | None = None):
     """The reference's dispatch (:25-45) with its names; "adamw_torch" and "lion" are the fused HIP steps.
-    `grad_accum_dtype=torch.float32`: fp32 gradient accumulation (the fused steps only)."""
+    `grad_accum_dtype=torch.float32`: fp32 gradient accumulation; `shard_group` / `shard`: state sharded over the learner ranks
+    (the fused steps only)."""
     grouped_params = get_grouped_params(model, weight_decay)
     if grad_accum_dtype is not None and name not in ("adamw_torch", "lion"):
         raise ValueError(f'grad_accum_dtype needs a fused optimizer ("adamw_torch" or "lion"), not "{name}"')
+    if (shard_group is not None or shard is not None) and name not in ("adamw_torch", "lion"):
+        raise ValueError(f'sharded optimizer state needs a fused optimizer ("adamw_torch" or "lion"), not "{name}"')
     if name == "adamw_torch":
-        return FusedAdamW(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype)
+        return FusedAdamW(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype, shard_group=shard_group, shard=shard)
     if name == "adafactor":
         from transformers import Adafactor
 
@@ -452,5 +866,5 @@ def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weigh
             raise ImportError(f'optimizer "cpuadam" needs the deepspeed package: {e}') from e
         return deepspeed.ops.adam.DeepSpeedCPUAdam(grouped_params, lr=learning_rate)
     if name == "lion":
-        return FusedLion(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype)
+        return FusedLion(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype, shard_group=shard_group, shard=shard)
     raise ValueError(f"Unknown optimizer: {name}")

@@ -78,6 +78,7 @@ class PipelineSpec:
     learner: str = "streamed"          # "streamed" (StreamedLearnerStep) or "dropin" (LearnerStep + rl_step_fused_head)
     optimizer: str = "adamw"           # "adamw" | "adamw_hip" (finetune/optim.py FusedAdamW) | "sgd" (parity tests)
     grad_accum_fp32: bool = False      # fold every micro-batch's gradients into fp32 accumulators (FusedAdamW(grad_accum_dtype=torch.float32)); needs "adamw_hip"
+    shard_optimizer_state: bool = False  # ZeRO-1: each learner rank keeps the fused optimizer's fp32 state for 1/n_learners of the parameters (FusedAdamW(shard_group=...)); needs "adamw_hip"
     param_dtype: str = "bf16"          # "bf16" (the reference's training dtype) | "fp32" (parity tests: tight parameter deltas)
     kl_coef: float = 0.0               # > 0 (configs[4]: 0.001): KL-to-reference on - the preprocessor holds the frozen reference policy (the initial policy) and writes `ref_logprobs`
     ref_seed: int | None = None        # seed of the reference policy (default: `seed`, i.e. the policy the run starts from)
@@ -110,6 +111,8 @@ class PipelineSpec:
                              "(the launcher rounds gradient_accumulation_passes up to a multiple of the learner count, launch.py:631-640)")
         if self.grad_accum_fp32 and self.optimizer != "adamw_hip":
             raise ValueError(f"grad_accum_fp32 folds gradients with the fused optimizer's kernel: it needs optimizer='adamw_hip', not {self.optimizer!r}")
+        if self.shard_optimizer_state and self.optimizer != "adamw_hip":
+            raise ValueError(f"shard_optimizer_state partitions the fused optimizer's state: it needs optimizer='adamw_hip', not {self.optimizer!r}")
         if self.weight_transport not in ("ipc", "rccl", "gloo"):
             raise ValueError(f"weight_transport {self.weight_transport!r}: 'ipc', 'rccl' or 'gloo'")
         if self.weight_transport == "ipc" and not self.share_device:
@@ -599,7 +602,8 @@ def learner_stage(spec: PipelineSpec, rank: int = 0, name: str = "learner") -> N
     elif spec.optimizer == "adamw_hip":
         from .finetune.optim import FusedAdamW
 
-        opt = FusedAdamW(train_model.parameters(), lr=spec.lr, grad_accum_dtype=torch.float32 if spec.grad_accum_fp32 else None)
+        shard_group = torch.distributed.group.WORLD if spec.shard_optimizer_state and world > 1 else None  # one learner: nothing to shard
+        opt = FusedAdamW(train_model.parameters(), lr=spec.lr, grad_accum_dtype=torch.float32 if spec.grad_accum_fp32 else None, shard_group=shard_group)
     else:
         opt = torch.optim.AdamW(train_model.parameters(), lr=spec.lr, fused=cuda)
     rl = rl_config_of(spec)

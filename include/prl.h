@@ -46,6 +46,7 @@
  *   prl_bucket_*                  pipelinerl/finetune_loop.py:205-292,
  *                                 pipelinerl/vllm1.py:62-134,
  *                                 pipelinerl/torch_utils.py:70-94
+ *   prl_adafactor_*               pipelinerl/finetune/optim.py:33-36 (transformers' Adafactor)
  *   prl_optim_*                   pipelinerl/finetune/optim.py:25-112 (AdamW / Lion) and the
  *                                 clip_grad_norm_ + optimizer.step() of pipelinerl/finetune_loop.py:738-744
  */
@@ -59,7 +60,7 @@
 extern "C" {
 #endif
 
-#define PRL_ABI_VERSION 16
+#define PRL_ABI_VERSION 17
 
 #define PRL_OK 0
 #define PRL_EINVAL (-22)   /* bad argument                                  */
@@ -674,6 +675,44 @@ typedef struct prl_accum_segment {
 } prl_accum_segment;
 int prl_optim_grad_accumulate(const prl_accum_segment* segments, int64_t n_segments,
                               int32_t overwrite, prl_stream_t stream);
+
+/* ---- Adafactor step (the reference's get_optimizer("adafactor"): transformers' Adafactor with relative_step=False,
+ * scale_parameter=False, beta1=None) ------------------------------------------------------------------------------
+ * Per parameter, with g = grad * norm_and_coef[1] (NULL = 1; the gradients are not rewritten), beta2t = 1 - step^decay_rate
+ * (double, rounded to fp32 once) and update = g^2 + eps1:
+ *   factored (`v == NULL`; a batch of `batch` matrices [rows, cols]; `row` is fp32 [batch, rows], `col` fp32 [batch, cols]):
+ *     row = row beta2t + mean over cols(update) (1 - beta2t);  col = col beta2t + mean over rows(update) (1 - beta2t)
+ *     u = rsqrt(row / mean over rows(row))[r] rsqrt(col)[c] g
+ *   unfactored (`v` fp32 of cols elements, batch = rows = 1):  v = v beta2t + update (1 - beta2t);  u = rsqrt(v) g
+ *   u /= max(1, rms(u) / clip_threshold)   (rms over the whole parameter);   p += p (-weight_decay lr) when weight_decay != 0;
+ *   p -= lr u.   `master` as in prl_optim_segment: the fp32 weights of a bf16 parameter, which is then only written (RNE).
+ * Every sum runs in fp64 in a fixed order without atomics: results are bitwise reproducible.  `segments` is a HOST array of
+ * device pointers; a segment with `grad == NULL` or no elements is skipped; the table is cut into launch groups and each group
+ * takes six launches; nothing allocates or synchronises; arguments are validated before any device work (PRL_EINVAL names
+ * the segment).  Rows that do not all start 16-byte aligned take a scalar path.
+ * prl_adafactor_workspace_bytes: the bytes `workspace` (device, 16-byte aligned) must have for this table: the records of the
+ *   largest launch group.  prl_adafactor_geometry reports the tile (rows per band, columns per tile) and the group limits. */
+typedef struct prl_adafactor_segment {
+  void* param;
+  const void* grad;
+  void* master;
+  void* row;
+  void* col;
+  void* v;
+  int64_t batch;
+  int64_t rows;
+  int64_t cols;
+  int64_t step;
+  int32_t param_dtype; /* PRL_DTYPE_* */
+  int32_t grad_dtype;  /* PRL_DTYPE_* */
+  double lr;
+  double weight_decay;
+} prl_adafactor_segment;
+int prl_adafactor_workspace_bytes(const prl_adafactor_segment* segments, int64_t n_segments, size_t* bytes);
+int prl_adafactor_step(const prl_adafactor_segment* segments, int64_t n_segments, double eps1, double clip_threshold,
+                       double decay_rate, const float* norm_and_coef, void* workspace, size_t workspace_bytes,
+                       prl_stream_t stream);
+int prl_adafactor_geometry(int64_t* band_rows, int64_t* tile_cols, int64_t* group_segments, int64_t* group_elements);
 
 /* ------------------------------------------------------------------------- */
 /* Fused output head: hidden states -> new_logprobs / entropy, logits never   */

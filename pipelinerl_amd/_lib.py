@@ -13,7 +13,7 @@ from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libprl.so"
 
-PRL_ABI_VERSION = 16
+PRL_ABI_VERSION = 17
 PRL_OK = 0
 PRL_EINVAL = -22
 PRL_ENOMEM = -12
@@ -140,6 +140,14 @@ class PrlOptimSegment(ctypes.Structure):
                 ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double)]
 
 
+class PrlAdafactorSegment(ctypes.Structure):
+    """Mirror of `struct prl_adafactor_segment` (include/prl.h)."""
+
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("master", c_void_p), ("row", c_void_p), ("col", c_void_p), ("v", c_void_p),
+                ("batch", c_int64), ("rows", c_int64), ("cols", c_int64), ("step", c_int64), ("param_dtype", c_int32), ("grad_dtype", c_int32),
+                ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double)]
+
+
 class PrlError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libprl error {code}: {message}")
@@ -220,6 +228,9 @@ PROTOTYPES: dict[str, tuple] = {
     "prl_optim_adamw_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
     "prl_optim_lion_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, _P, _P]),
     "prl_optim_grad_accumulate": (c_int32, [_P, c_int64, c_int32, _P]),
+    "prl_adafactor_workspace_bytes": (c_int32, [_P, c_int64, POINTER(c_size_t)]),
+    "prl_adafactor_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, c_size_t, _P]),
+    "prl_adafactor_geometry": (c_int32, [POINTER(c_int64)] * 4),
     "prl_lm_head_prepare": (c_int32, [c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, _P]),
     "prl_lm_head_workspace_bytes": (c_int32, [c_int64, c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t), POINTER(c_size_t)]),
     "prl_lm_head_logprob_fwd": (c_int32, [c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_size_t, _P]),

@@ -50,6 +50,10 @@ reduce the last micro-batch's `p.grad` only).  fp32 gradients (the fp32 `lm_head
 into in fp32) are used as they are.  The accumulators are views of one flat buffer, transient (not in `state_dict()`), and
 cost 4 bytes per bf16 element: 28 GB on the Qwen2.5-7B list.
 
+`FusedAdafactor` (`get_optimizer("adafactor_hip")`) is transformers' Adafactor with the reference's flags on the same host side
+(csrc/prl_adafactor.hip): the same boundary protocol, master weights and fp32 accumulation; factored state under transformers'
+keys; no sharded state.
+
 There is no CPU path: parameters that are not on a HIP device raise.
 """
 
@@ -166,6 +170,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
     """Shared host side of the fused steps: lazily allocated flat fp32 state, the segment table, the norm record."""
 
     _state_keys: tuple[str, ...] = ("exp_avg",)
+    _segment_type = _lib.PrlOptimSegment  # what `_launch` hands to `_call`
 
     def __init__(self, params: Iterable, defaults: dict[str, Any], master_weights: bool, grad_accum_dtype: torch.dtype | None = None,
                  shard_group=None, shard: tuple[int, int] | None = None):
@@ -202,6 +207,10 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def _keys_of(self, p: torch.Tensor) -> tuple[str, ...]:
         return self._state_keys + (("master",) if self._wants_master(p) else ())
 
+    def _state_shape(self, p: torch.Tensor, key: str) -> torch.Size:
+        """Shape of `state[p][key]`: the parameter's, unless the rule keeps less (Adafactor's row / column averages)."""
+        return p.shape
+
     def _is_flat_view(self, t: torch.Tensor) -> bool:
         return any(t.untyped_storage().data_ptr() == f.untyped_storage().data_ptr() for f in self._flat)
 
@@ -226,16 +235,17 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 owners = [p for p in todo if key in self._keys_of(p)]
                 if not owners:
                     continue
-                slots = [(-(-p.numel() // _SLOT)) * _SLOT for p in owners]
+                shapes = [self._state_shape(p, key) for p in owners]
+                slots = [(-(-shape.numel() // _SLOT)) * _SLOT for shape in shapes]
                 flat = torch.zeros(sum(slots), dtype=torch.float32, device=device)
                 self._flat.append(flat)
                 off = 0
-                for p, slot in zip(owners, slots):
-                    view = flat[off:off + p.numel()].view(p.shape)
+                for p, slot, shape in zip(owners, slots, shapes):
+                    view = flat[off:off + shape.numel()].view(shape)
                     off += slot
                     st = self.state[p]
                     if key in st:  # loaded from a checkpoint: keep its values
-                        view.copy_(st[key].to(device=device, dtype=torch.float32).reshape(p.shape))
+                        view.copy_(st[key].to(device=device, dtype=torch.float32).reshape(shape))
                     elif key == "master":
                         view.copy_(p.detach())
                     st[key] = view
@@ -589,9 +599,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
             seg.grad = g.data_ptr() + b * g.element_size() if g is not None and p.numel() else None
             seg.grad_dtype = _DTYPES[g.dtype] if g is not None else _DTYPES[p.dtype]
             if g is not None:
-                seg.exp_avg = st["exp_avg"].data_ptr()
-                seg.exp_avg_sq = st["exp_avg_sq"].data_ptr() if "exp_avg_sq" in st else None
-                seg.master = st["master"].data_ptr() if "master" in st else None
+                self._fill_state(seg, st)
         self._norm_table = None
         if self._shard is not None and self.grad_accum_dtype is None:  # complete gradients on every rank: the norm reads them whole
             self._norm_table = (_lib.PrlOptimSegment * max(len(everything), 1))()
@@ -613,6 +621,11 @@ class _FusedOptimizer(torch.optim.Optimizer):
             _lib.check(_lib.load().prl_optim_workspace_bytes(len(entries), sum(p.numel() for p, _ in entries), ctypes.byref(need)))
             if self._workspace is None or self._workspace.numel() < need.value:
                 self._workspace = torch.empty(max(need.value, 8), dtype=torch.uint8, device=device)
+
+    def _fill_state(self, seg, st: dict) -> None:
+        seg.exp_avg = st["exp_avg"].data_ptr()
+        seg.exp_avg_sq = st["exp_avg_sq"].data_ptr() if "exp_avg_sq" in st else None
+        seg.master = st["master"].data_ptr() if "master" in st else None
 
     def _key(self, entries) -> list[tuple]:
         grads = [self._grad_of(p) for p, _ in entries]  # an accumulator where one is filled: another address AND another dtype
@@ -797,7 +810,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 continue
             k = sum(sizes[first:i + 1])
             if k:
-                sub = ctypes.byref(table, off * ctypes.sizeof(_lib.PrlOptimSegment))
+                sub = ctypes.byref(table, off * ctypes.sizeof(self._segment_type))
                 self._call(lib, sub, k, keys[first], record)
             off += k
             first = i + 1
@@ -843,12 +856,124 @@ class FusedLion(_FusedOptimizer):
         _lib.check(lib.prl_optim_lion_step(table, n, key[0], key[1], record, self._stream()))
 
 
+class FusedAdafactor(_FusedOptimizer):
+    """transformers' `Adafactor(relative_step=False, scale_parameter=False)` - what the reference builds for "adafactor" - as six
+    fused launches per 32 parameters (csrc/prl_adafactor.hip): factored second moments for every parameter with two or more
+    dimensions (the leading ones are a batch of matrices), the update clipped by its own rms over the whole parameter.  fp32
+    state under transformers' keys (`step`, `exp_avg_sq_row`, `exp_avg_sq_col` or `exp_avg_sq`; `RMS`, which the rule never reads,
+    is not kept) plus `master` for bf16 parameters; a `transformers.Adafactor` `state_dict()` over the same parameters loads (the
+    master copy is then seeded from the parameter), and this class's state without `master` loads into `transformers.Adafactor`.
+    The boundary protocol is the fused optimizers': `accumulate_grads`, `reduce_accumulated`, `compute_grad_norm`, `clip_and_step`.
+    `beta1`, `relative_step` and `scale_parameter` are not built, and neither is sharded state: row and column averages do not cut
+    into element ranges."""
+
+    _state_keys = ("exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_sq")  # every key a parameter can have: `_keys_of` picks
+
+    def __init__(self, params, lr: float = 1e-3, eps1: float = 1e-30, clip_threshold: float = 1.0, decay_rate: float = -0.8, weight_decay: float = 0.0,
+                 master_weights: bool = True, grad_accum_dtype: torch.dtype | None = None, beta1=None, relative_step: bool = False,
+                 scale_parameter: bool = False, shard_group=None, shard: tuple[int, int] | None = None):
+        unsupported = [n for n, on in (("beta1", beta1 is not None), ("relative_step", relative_step), ("scale_parameter", scale_parameter)) if on]
+        if unsupported:
+            raise ValueError(f"FusedAdafactor: {', '.join(unsupported)} not supported (the fused step is the reference's rule: beta1=None, "
+                             "relative_step=False, scale_parameter=False)")
+        if shard_group is not None or shard is not None:
+            raise ValueError("FusedAdafactor: sharded optimizer state is not built for Adafactor (row and column averages do not cut into element ranges)")
+        if lr is None or not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps1:
+            raise ValueError(f"Invalid epsilon value: {eps1}")
+        if not 0.0 < clip_threshold:
+            raise ValueError(f"Invalid clip_threshold value: {clip_threshold}")
+        if not decay_rate <= 0.0:
+            raise ValueError(f"Invalid decay_rate value: {decay_rate}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        # transformers' group keys, so that a state dictionary travels both ways (eps[1] belongs to scale_parameter and is never read)
+        defaults = dict(lr=lr, eps=(eps1, 1e-3), clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=None, weight_decay=weight_decay,
+                        scale_parameter=False, relative_step=False, warmup_init=False)
+        super().__init__(params, defaults, master_weights, grad_accum_dtype)
+        self._ada_table = None
+        self._ada_workspace: torch.Tensor | None = None
+
+    @staticmethod
+    def _factored(p: torch.Tensor) -> bool:
+        return p.dim() >= 2
+
+    def _keys_of(self, p):
+        keys = ("exp_avg_sq_row", "exp_avg_sq_col") if self._factored(p) else ("exp_avg_sq",)
+        return keys + (("master",) if self._wants_master(p) else ())
+
+    def _state_shape(self, p, key):
+        if key == "exp_avg_sq_row":
+            return p.shape[:-1]
+        if key == "exp_avg_sq_col":
+            return p.shape[:-2] + p.shape[-1:]
+        return p.shape
+
+    def _fill_state(self, seg, st):
+        pass  # the norm pass reads gradients only; the step has its own table
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            if group.get("beta1") is not None or group.get("relative_step") or group.get("scale_parameter"):
+                raise ValueError("FusedAdafactor: the loaded param_groups use beta1, relative_step or scale_parameter, which are not supported")
+        for st in self.state.values():
+            st.pop("RMS", None)
+        self._ada_table = None
+
+    def _build_table(self) -> None:
+        super()._build_table()
+        entries = self._table_params
+        table = (_lib.PrlAdafactorSegment * max(len(entries), 1))()
+        for seg, (p, _) in zip(table, entries):
+            g = self._grad_of(p)
+            seg.param, seg.param_dtype = p.data_ptr(), _DTYPES[p.dtype]
+            seg.grad = g.data_ptr() if g is not None and p.numel() else None
+            seg.grad_dtype = _DTYPES[g.dtype] if g is not None else _DTYPES[p.dtype]
+            if self._factored(p):
+                seg.rows, seg.cols = p.shape[-2], p.shape[-1]
+                seg.batch = p.numel() // (seg.rows * seg.cols) if seg.rows * seg.cols else 0
+            else:
+                seg.batch, seg.rows, seg.cols = 1, 1, p.numel()
+            if g is not None:
+                st = self.state[p]
+                seg.row = st["exp_avg_sq_row"].data_ptr() if "exp_avg_sq_row" in st else None
+                seg.col = st["exp_avg_sq_col"].data_ptr() if "exp_avg_sq_col" in st else None
+                seg.v = st["exp_avg_sq"].data_ptr() if "exp_avg_sq" in st else None
+                seg.master = st["master"].data_ptr() if "master" in st else None
+                seg.step = 1  # (the table is sized with a valid step; the real one is written before every launch)
+        self._ada_table = table
+        if entries:
+            need = ctypes.c_size_t(0)
+            _lib.check(_lib.load().prl_adafactor_workspace_bytes(table, len(entries), ctypes.byref(need)))
+            if self._ada_workspace is None or self._ada_workspace.numel() < need.value:
+                self._ada_workspace = torch.empty(max(need.value, 16), dtype=torch.uint8, device=self._device)
+
+    def _launch(self, lib, table, n: int, record: int | None) -> None:
+        """One call per run of consecutive groups that agree on the launch-level constants (eps1, clip_threshold, decay_rate)."""
+        for seg, ada in zip(table, self._ada_table):
+            ada.step, ada.lr, ada.weight_decay = seg.step, seg.lr, seg.weight_decay
+        super()._launch(lib, self._ada_table, n, record)
+
+    _segment_type = _lib.PrlAdafactorSegment
+
+    def _launch_key(self, group):
+        return (float(group["eps"][0]), float(group["clip_threshold"]), float(group["decay_rate"]))
+
+    def _call(self, lib, table, n, key, record):
+        _lib.check(lib.prl_adafactor_step(table, n, key[0], key[1], key[2], record, self._ada_workspace.data_ptr(), self._ada_workspace.numel(), self._stream()))
+
+
 def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weight_decay: float, grad_accum_dtype: torch.dtype | None = None,
                   shard_group=None, shard: tuple[int, int] | None = None):
-    """The reference's dispatch (:25-45) with its names; "adamw_torch" and "lion" are the fused HIP steps.
-    `grad_accum_dtype=torch.float32`: fp32 gradient accumulation; `shard_group` / `shard`: state sharded over the learner ranks
-    (the fused steps only)."""
+    """The reference's dispatch (:25-45) with its names; "adamw_torch" and "lion" are the fused HIP steps, "adafactor_hip" is the
+    fused HIP form of "adafactor" (which stays transformers' class).
+    `grad_accum_dtype=torch.float32`: fp32 gradient accumulation (the fused steps only); `shard_group` / `shard`: state sharded over
+    the learner ranks ("adamw_torch" and "lion" only)."""
     grouped_params = get_grouped_params(model, weight_decay)
+    if name == "adafactor_hip":
+        return FusedAdafactor(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype, shard_group=shard_group, shard=shard)
     if grad_accum_dtype is not None and name not in ("adamw_torch", "lion"):
         raise ValueError(f'grad_accum_dtype needs a fused optimizer ("adamw_torch" or "lion"), not "{name}"')
     if (shard_group is not None or shard is not None) and name not in ("adamw_torch", "lion"):

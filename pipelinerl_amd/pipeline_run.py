@@ -76,8 +76,8 @@ class PipelineSpec:
     engine_load: bool = False          # the engine runs forward passes between updates (a colocated actor's GPU share)
     gradient_checkpointing: bool = False
     learner: str = "streamed"          # "streamed" (StreamedLearnerStep) or "dropin" (LearnerStep + rl_step_fused_head)
-    optimizer: str = "adamw"           # "adamw" | "adamw_hip" (finetune/optim.py FusedAdamW) | "sgd" (parity tests)
-    grad_accum_fp32: bool = False      # fold every micro-batch's gradients into fp32 accumulators (FusedAdamW(grad_accum_dtype=torch.float32)); needs "adamw_hip"
+    optimizer: str = "adamw"           # "adamw" | "adamw_hip" (finetune/optim.py FusedAdamW) | "adafactor_hip" (FusedAdafactor) | "sgd" (parity tests)
+    grad_accum_fp32: bool = False      # fold every micro-batch's gradients into fp32 accumulators (grad_accum_dtype=torch.float32 of the fused optimizers); needs "adamw_hip" or "adafactor_hip"
     shard_optimizer_state: bool = False  # ZeRO-1: each learner rank keeps the fused optimizer's fp32 state for 1/n_learners of the parameters (FusedAdamW(shard_group=...)); needs "adamw_hip"
     param_dtype: str = "bf16"          # "bf16" (the reference's training dtype) | "fp32" (parity tests: tight parameter deltas)
     kl_coef: float = 0.0               # > 0 (configs[4]: 0.001): KL-to-reference on - the preprocessor holds the frozen reference policy (the initial policy) and writes `ref_logprobs`
@@ -109,8 +109,8 @@ class PipelineSpec:
         if self.global_batch % self.n_learners:
             raise ValueError(f"global_batch {self.global_batch} does not split into {self.n_learners} equal per-learner quotas "
                              "(the launcher rounds gradient_accumulation_passes up to a multiple of the learner count, launch.py:631-640)")
-        if self.grad_accum_fp32 and self.optimizer != "adamw_hip":
-            raise ValueError(f"grad_accum_fp32 folds gradients with the fused optimizer's kernel: it needs optimizer='adamw_hip', not {self.optimizer!r}")
+        if self.grad_accum_fp32 and self.optimizer not in ("adamw_hip", "adafactor_hip"):
+            raise ValueError(f"grad_accum_fp32 folds gradients with the fused optimizer's kernel: it needs optimizer='adamw_hip' or 'adafactor_hip', not {self.optimizer!r}")
         if self.shard_optimizer_state and self.optimizer != "adamw_hip":
             raise ValueError(f"shard_optimizer_state partitions the fused optimizer's state: it needs optimizer='adamw_hip', not {self.optimizer!r}")
         if self.weight_transport not in ("ipc", "rccl", "gloo"):
@@ -599,6 +599,10 @@ def learner_stage(spec: PipelineSpec, rank: int = 0, name: str = "learner") -> N
         train_model = torch.nn.parallel.DistributedDataParallel(model, **({"device_ids": [dev.index]} if cuda and spec.learner_backend == "nccl" else {}))
     if spec.optimizer == "sgd":
         opt = torch.optim.SGD(train_model.parameters(), lr=spec.lr)
+    elif spec.optimizer == "adafactor_hip":
+        from .finetune.optim import FusedAdafactor
+
+        opt = FusedAdafactor(train_model.parameters(), lr=spec.lr, grad_accum_dtype=torch.float32 if spec.grad_accum_fp32 else None)
     elif spec.optimizer == "adamw_hip":
         from .finetune.optim import FusedAdamW
 

@@ -19,6 +19,15 @@ own under its own time limit; the first one that fails ends the run.  One JSON o
 all three in ONE child process on the same gradients, HIP events around each repetition, 20 repetitions after warm-up, median [min, max].
 
     python scripts/optim_step_bench.py --mode grad_accum --out profiles/grad_accum_bench.json
+
+`--mode adafactor` times the Adafactor boundary on the Qwen2.5-0.5B parameter list (bf16 parameters and gradients; the embeddings are tied, so there is no separate head):
+
+  fused_adafactor  FusedAdafactor.clip_and_step, master weights on                    (norm 2 + step 2 + 2 + 2 + 4 read, 4 + 2 written = 18 B per bf16 element)
+  transformers     clip_grad_norm_ + transformers.Adafactor(relative_step=False, scale_parameter=False).step() on a twin parameter set
+
+both in ONE child process, alternating, HIP events around each boundary, 20 boundaries after warm-up, median [min, max].
+
+    python scripts/optim_step_bench.py --mode adafactor --out profiles/adafactor_step_bench.json
 """
 
 from __future__ import annotations
@@ -156,6 +165,78 @@ def run_grad_accum(steps: int, warmup: int) -> dict:
     return out
 
 
+def run_adafactor(steps: int, warmup: int, max_norm: float) -> dict:
+    import torch
+    from transformers.optimization import Adafactor
+
+    from pipelinerl_amd.finetune.optim import FusedAdafactor
+    from pipelinerl_amd.weight_sync_probe import qwen25_shapes
+
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    sets = ([], [])
+    for name, shape in qwen25_shapes("0p5b"):
+        dtype = torch.float32 if name == "lm_head.weight" else torch.bfloat16
+        w = torch.empty(shape, dtype=dtype, device=dev).normal_(0.0, 0.02, generator=gen)
+        g = torch.empty(shape, dtype=dtype, device=dev).normal_(0.0, 1e-3, generator=gen)
+        for params in sets:
+            p = torch.nn.Parameter(w.clone())
+            p.grad = g.clone()
+            params.append(p)
+    fused = FusedAdafactor(sets[0], lr=1e-6, master_weights=True)
+    stock = Adafactor(sets[1], lr=1e-6, relative_step=False, scale_parameter=False)
+
+    calls = {"fused_adafactor": lambda: fused.clip_and_step(max_norm), "transformers": None}
+    times = {k: [] for k in calls}
+    for k in range(warmup + steps):  # alternating: the two see the same clocks
+        for name in calls:
+            if name == "transformers":
+                saved = [p.grad.clone() for p in sets[1]]
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            if name == "transformers":
+                torch.nn.utils.clip_grad_norm_(sets[1], max_norm)
+                stock.step()
+            else:
+                calls[name]()
+            b.record()
+            b.synchronize()
+            if name == "transformers":  # clip_grad_norm_ rescaled the gradients in place: put them back, outside the timed window
+                for p, g in zip(sets[1], saved):
+                    p.grad = g
+            if k >= warmup:
+                times[name].append(a.elapsed_time(b))
+    alg = 0
+    for p in sets[0]:
+        e = p.element_size()
+        alg += p.numel() * (e + 3 * e + (4 + 4 + 2 if e == 2 else 4 + 4))  # norm; three reads of the gradient; weights read and written (+ the bf16 image)
+    out = {"tensors": len(sets[0]), "numel": sum(p.numel() for p in sets[0]), "steps": steps, "warmup": warmup, "max_norm": max_norm, "results": {}}
+    for name, t in times.items():
+        out["results"][name] = {"median_ms": statistics.median(t), "min_ms": min(t), "max_ms": max(t)}
+    r = out["results"]["fused_adafactor"]
+    gbs = alg / (r["median_ms"] * 1e-3) / 1e9
+    r.update(algorithmic_bytes=alg, achieved_gbs=gbs, frac_of_peak=gbs / PEAK_GBS, frac_of_copy_ceiling=gbs / COPY_CEILING_GBS)
+    return out
+
+
+def main_adafactor(args) -> None:
+    cmd = [sys.executable, __file__, "--one", "adafactor", "--steps", str(args.steps), "--warmup", str(args.warmup), "--max-norm", str(args.max_norm)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
+    line = next((l for l in res.stdout.splitlines() if l.startswith("RESULT ")), None)
+    if res.returncode != 0 or line is None:
+        raise SystemExit(f"adafactor: exit status {res.returncode}\n{res.stdout[-2000:]}\n{res.stderr[-4000:]}")
+    report = json.loads(line[len("RESULT "):])
+    r = report["results"]
+    report = {"workload": "Qwen2.5-0.5B parameter list (tied embeddings: no separate head), bf16 parameters and gradients, Adafactor, clip at %g" % args.max_norm, **report,
+              "spread_transformers_ms": r["transformers"]["max_ms"] - r["transformers"]["min_ms"],
+              "gain_ms": r["transformers"]["median_ms"] - r["fused_adafactor"]["median_ms"]}
+    text = json.dumps(report, indent=1)
+    print(text)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(text + "\n")
+
+
 def main_grad_accum(args) -> None:
     cmd = [sys.executable, __file__, "--one", "grad_accum", "--steps", str(args.steps), "--warmup", str(args.warmup)]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
@@ -182,14 +263,21 @@ def main() -> None:
     ap.add_argument("--max-norm", type=float, default=0.3)
     ap.add_argument("--timeout", type=int, default=300, help="seconds per configuration")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--mode", choices=("boundary", "grad_accum"), default="boundary", help="what to time: the step boundary, or the fp32 gradient fold")
-    ap.add_argument("--one", choices=CONFIGS + ("grad_accum",), default=None, help="(child) run one configuration in this process")
+    ap.add_argument("--mode", choices=("boundary", "grad_accum", "adafactor"), default="boundary",
+                    help="what to time: the AdamW step boundary, the fp32 gradient fold, or the Adafactor boundary")
+    ap.add_argument("--one", choices=CONFIGS + ("grad_accum", "adafactor"), default=None, help="(child) run one configuration in this process")
     args = ap.parse_args()
     if args.one == "grad_accum":
         print("RESULT " + json.dumps(run_grad_accum(args.steps, args.warmup)), flush=True)
         return
     if args.mode == "grad_accum":
         main_grad_accum(args)
+        return
+    if args.one == "adafactor":
+        print("RESULT " + json.dumps(run_adafactor(args.steps, args.warmup, args.max_norm)), flush=True)
+        return
+    if args.mode == "adafactor":
+        main_adafactor(args)
         return
     if args.one:
         print("RESULT " + json.dumps(run_one(args.one, args.steps, args.warmup, args.max_norm)), flush=True)

@@ -60,7 +60,7 @@
 extern "C" {
 #endif
 
-#define PRL_ABI_VERSION 17
+#define PRL_ABI_VERSION 18
 
 #define PRL_OK 0
 #define PRL_EINVAL (-22)   /* bad argument                                  */
@@ -657,6 +657,47 @@ int prl_optim_adamw_step(const prl_optim_segment* segments, int64_t n_segments, 
                          const float* norm_and_coef, prl_stream_t stream);
 int prl_optim_lion_step(const prl_optim_segment* segments, int64_t n_segments, double beta1, double beta2,
                         const float* norm_and_coef, prl_stream_t stream);
+
+/* The same steps with compact state (csrc/prl_optim_compact.hip): the moments kept in bf16 and / or a bf16 parameter
+ * without a master copy, every such bf16 store rounded STOCHASTICALLY so that updates below half an ulp survive in
+ * expectation.  The arithmetic is the one above, unchanged and in fp32: bf16 state is widened exactly on load.
+ *   `state_dtype` PRL_DTYPE_BF16: `exp_avg` / `exp_avg_sq` are bf16 arrays, stored with stochastic rounding;
+ *     PRL_DTYPE_F32: fp32 arrays as above.
+ *   `param_rounding` PRL_ROUND_STOCHASTIC: a bf16 parameter without `master` is written with stochastic rounding
+ *     (PRL_ROUND_NEAREST: to nearest even, as above).  With `master` it is PRL_EINVAL: the master is the truth and the
+ *     parameter its nearest image.  An fp32 parameter is written exactly either way.
+ *   Rounding (csrc/prl_optim_sr.h): sr(f, r) = (bits(f) + r) >> 16 with r uniform on 0 .. 65535; NaN -> 0x7FC0.  The r come
+ *     from Philox4x32-10 with key (seed lo, seed hi) and counter (q lo, q hi, step, ordinal), q = (elem_offset + index in
+ *     the segment) / 4; element 4q + j takes output word j = x: r = x & 0xffff for the parameter, x >> 16 for exp_avg,
+ *     their xor for exp_avg_sq.  `elem_offset` = index of the segment's first element inside its parameter (>= 0, a
+ *     multiple of 4; 0 for a whole parameter), `ordinal` = the parameter's number (0 .. 2^32 - 1), `step` enters with
+ *     its low 32 bits: a piece of a parameter is rounded exactly as inside the whole, and a resumed run continues bit
+ *     for bit.
+ *   The promises of the calls above hold: HOST table of device pointers, nothing allocates or synchronises, arguments
+ *   are validated before any device work (PRL_EINVAL names the segment), unaligned pointers take a scalar path. */
+#define PRL_ROUND_NEAREST 0
+#define PRL_ROUND_STOCHASTIC 1
+typedef struct prl_optim_compact_segment {
+  void* param;
+  const void* grad;
+  void* master;
+  void* exp_avg;
+  void* exp_avg_sq;
+  int64_t numel;
+  int64_t step;
+  int32_t param_dtype; /* PRL_DTYPE_* */
+  int32_t grad_dtype;  /* PRL_DTYPE_* */
+  double lr;
+  double weight_decay;
+  int32_t state_dtype;    /* PRL_DTYPE_* */
+  int32_t param_rounding; /* PRL_ROUND_* */
+  int64_t elem_offset;
+  int64_t ordinal;
+} prl_optim_compact_segment;
+int prl_optim_adamw_step_compact(const prl_optim_compact_segment* segments, int64_t n_segments, double beta1, double beta2,
+                                 double eps, uint64_t seed, const float* norm_and_coef, prl_stream_t stream);
+int prl_optim_lion_step_compact(const prl_optim_compact_segment* segments, int64_t n_segments, double beta1, double beta2,
+                                uint64_t seed, const float* norm_and_coef, prl_stream_t stream);
 
 /* Gradient accumulation in fp32: folds ONE micro-batch's gradients into the accumulators the calls above then
  * read as `grad` (grad_dtype PRL_DTYPE_F32).  Autograd sums micro-batch gradients in the parameter's dtype; a

@@ -13,7 +13,7 @@ from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libprl.so"
 
-PRL_ABI_VERSION = 17
+PRL_ABI_VERSION = 18
 PRL_OK = 0
 PRL_EINVAL = -22
 PRL_ENOMEM = -12
@@ -140,6 +140,15 @@ class PrlOptimSegment(ctypes.Structure):
                 ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double)]
 
 
+PRL_ROUND_NEAREST, PRL_ROUND_STOCHASTIC = 0, 1  # prl_optim_compact_segment.param_rounding
+
+
+class PrlOptimCompactSegment(ctypes.Structure):
+    """Mirror of `struct prl_optim_compact_segment` (include/prl.h): `prl_optim_segment` plus the rounding fields."""
+
+    _fields_ = PrlOptimSegment._fields_ + [("state_dtype", c_int32), ("param_rounding", c_int32), ("elem_offset", c_int64), ("ordinal", c_int64)]
+
+
 class PrlAdafactorSegment(ctypes.Structure):
     """Mirror of `struct prl_adafactor_segment` (include/prl.h)."""
 
@@ -227,6 +236,8 @@ PROTOTYPES: dict[str, tuple] = {
     "prl_optim_clip_from_sumsq": (c_int32, [_P, c_float, _P, _P]),
     "prl_optim_adamw_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
     "prl_optim_lion_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "prl_optim_adamw_step_compact": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_uint64, _P, _P]),
+    "prl_optim_lion_step_compact": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, c_uint64, _P, _P]),
     "prl_optim_grad_accumulate": (c_int32, [_P, c_int64, c_int32, _P]),
     "prl_adafactor_workspace_bytes": (c_int32, [_P, c_int64, POINTER(c_size_t)]),
     "prl_adafactor_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, c_size_t, _P]),

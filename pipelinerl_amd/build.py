@@ -42,6 +42,7 @@ SOURCES = [
     "prl_pack.hip",
     "prl_copy.hip",
     "prl_optim.hip",
+    "prl_optim_compact.hip",
     "prl_adafactor.hip",
     "prl_lmhead_prepare.hip",
     "prl_lmhead_fwd.hip",

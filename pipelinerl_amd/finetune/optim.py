@@ -50,6 +50,19 @@ reduce the last micro-batch's `p.grad` only).  fp32 gradients (the fp32 `lm_head
 into in fp32) are used as they are.  The accumulators are views of one flat buffer, transient (not in `state_dict()`), and
 cost 4 bytes per bf16 element: 28 GB on the Qwen2.5-7B list.
 
+Compact state (`state_dtype=torch.bfloat16`, `param_rounding="stochastic"`, `seed=`; `FusedAdamW` / `FusedLion`, csrc/prl_optim_compact.hip):
+`exp_avg` / `exp_avg_sq` are kept in bf16 - widened exactly on load, the fp32 update unchanged, the store rounded STOCHASTICALLY - and a
+bf16 parameter without a master copy (`master_weights=False`) is written with stochastic rounding, so that an update below half an ulp
+survives in expectation instead of being rounded away (round-to-nearest cannot even decay a bf16 second moment: 0.999 v rounds back
+to v).  State per bf16 element: AdamW 12 -> 4 bytes, Lion 8 -> 2.  The two options are independent; `param_rounding="stochastic"` has
+no effect on a parameter that has a master copy (the master stays the truth and the parameter its nearest image) or is fp32 (written
+exactly).  The random bits are a pure function of (seed, parameter's index in `param_groups` order, element's index inside the
+parameter, step): Philox4x32-10, csrc/prl_optim_sr.h.  Hence a sharded run produces the bits of the unsharded one, two runs with one
+seed agree, and a run resumed from `state_dict()` (which carries `seed` in `param_groups` and the counter in `step`) continues bit for
+bit.  `state_dict()` holds the moments in `state_dtype`; `load_state_dict` converts a loaded moment to this optimizer's `state_dtype`
+(bf16 -> fp32 exactly; fp32 -> bf16 to nearest even, once).  The defaults (`torch.float32`, `"nearest"`) run the kernels and entry
+points above, untouched.
+
 `FusedAdafactor` (`get_optimizer("adafactor_hip")`) is transformers' Adafactor with the reference's flags on the same host side
 (csrc/prl_adafactor.hip): the same boundary protocol, master weights and fp32 accumulation; factored state under transformers'
 keys; no sharded state.
@@ -142,7 +155,7 @@ def merge_shard_state_dicts(shards: list[dict]) -> dict:
                     full[k] = torch.as_tensor(v, dtype=torch.float32).detach().cpu().clone()
                     continue
                 if k not in full:
-                    full[k] = torch.zeros(meta["numels"][pid], dtype=torch.float32, device=v.device)
+                    full[k] = torch.zeros(meta["numels"][pid], dtype=v.dtype, device=v.device)
                 full[k][b:e] = v.reshape(-1)
     for pid, st in state.items():
         for k in st:
@@ -166,16 +179,37 @@ def _check_hyper(lr: float, betas: tuple[float, float], weight_decay: float, eps
         raise ValueError(f"Invalid weight_decay value: {weight_decay}")
 
 
+_ROUNDINGS = {"nearest": _lib.PRL_ROUND_NEAREST, "stochastic": _lib.PRL_ROUND_STOCHASTIC}
+
+
+def _check_compact(state_dtype, param_rounding, seed) -> torch.dtype:
+    """Validates the compact-state options; returns the dtype of the moments (None means fp32)."""
+    state_dtype = torch.float32 if state_dtype is None else state_dtype
+    if state_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"fused optimizer: state_dtype must be torch.float32 or torch.bfloat16 (got {state_dtype})")
+    if param_rounding not in _ROUNDINGS:
+        raise ValueError(f'fused optimizer: param_rounding must be "nearest" or "stochastic" (got {param_rounding!r})')
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"fused optimizer: seed must be an int in [0, 2^64) (got {seed!r})")
+    return state_dtype
+
+
 class _FusedOptimizer(torch.optim.Optimizer):
-    """Shared host side of the fused steps: lazily allocated flat fp32 state, the segment table, the norm record."""
+    """Shared host side of the fused steps: lazily allocated flat state (fp32, or bf16 moments), the segment table, the norm record."""
 
     _state_keys: tuple[str, ...] = ("exp_avg",)
     _segment_type = _lib.PrlOptimSegment  # what `_launch` hands to `_call`
 
     def __init__(self, params: Iterable, defaults: dict[str, Any], master_weights: bool, grad_accum_dtype: torch.dtype | None = None,
-                 shard_group=None, shard: tuple[int, int] | None = None):
+                 shard_group=None, shard: tuple[int, int] | None = None, state_dtype: torch.dtype | None = None, param_rounding: str = "nearest"):
         if grad_accum_dtype not in (None, torch.float32):
             raise ValueError(f"fused optimizer: grad_accum_dtype must be None or torch.float32 (got {grad_accum_dtype})")
+        self.state_dtype = _check_compact(state_dtype, param_rounding, defaults.get("seed", 0))
+        self.param_rounding = param_rounding
+        self._compact = self.state_dtype != torch.float32 or param_rounding != "nearest"  # the step goes through the compact entry points
+        self._compact_table = None                # ctypes array of PrlOptimCompactSegment, entry for entry next to `_table`
+        if self._compact:
+            self._segment_type = _lib.PrlOptimCompactSegment
         self._shard = _resolve_shard(shard_group, shard)  # (rank, world), world > 1; None: unsharded
         self._shard_group = shard_group if self._shard is not None else None
         super().__init__(params, defaults)
@@ -207,6 +241,10 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def _keys_of(self, p: torch.Tensor) -> tuple[str, ...]:
         return self._state_keys + (("master",) if self._wants_master(p) else ())
 
+    def _dtype_of(self, key: str) -> torch.dtype:
+        """dtype of `state[p][key]`: `state_dtype` for the moments, fp32 for the master copy."""
+        return torch.float32 if key == "master" else self.state_dtype
+
     def _state_shape(self, p: torch.Tensor, key: str) -> torch.Size:
         """Shape of `state[p][key]`: the parameter's, unless the rule keeps less (Adafactor's row / column averages)."""
         return p.shape
@@ -225,7 +263,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
                     continue
                 st = self.state[p]
                 keys = self._keys_of(p)
-                if all(k in st and st[k].dtype == torch.float32 and st[k].device == p.device and self._is_flat_view(st[k]) for k in keys) and "step" in st:
+                if all(k in st and st[k].dtype == self._dtype_of(k) and st[k].device == p.device and self._is_flat_view(st[k]) for k in keys) and "step" in st:
                     continue
                 todo.append(p)
             if not todo:
@@ -237,7 +275,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
                     continue
                 shapes = [self._state_shape(p, key) for p in owners]
                 slots = [(-(-shape.numel() // _SLOT)) * _SLOT for shape in shapes]
-                flat = torch.zeros(sum(slots), dtype=torch.float32, device=device)
+                flat = torch.zeros(sum(slots), dtype=self._dtype_of(key), device=device)
                 self._flat.append(flat)
                 off = 0
                 for p, slot, shape in zip(owners, slots, shapes):
@@ -245,7 +283,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
                     off += slot
                     st = self.state[p]
                     if key in st:  # loaded from a checkpoint: keep its values
-                        view.copy_(st[key].to(device=device, dtype=torch.float32).reshape(shape))
+                        view.copy_(st[key].to(device=device, dtype=flat.dtype).reshape(shape))
                     elif key == "master":
                         view.copy_(p.detach())
                     st[key] = view
@@ -282,7 +320,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         device = params[0].device
         if not self._shard_flat:
             keys = self._state_keys + (("master",) if any(self._wants_master(p) for p in params) else ())
-            self._shard_flat = {k: torch.zeros(shard_len, dtype=torch.float32, device=device) for k in keys}
+            self._shard_flat = {k: torch.zeros(shard_len, dtype=self._dtype_of(k), device=device) for k in keys}
             self._flat = list(self._shard_flat.values())
         lo = self._shard[0] * shard_len
         for i, p in enumerate(params):
@@ -298,7 +336,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 if cur is not None:  # loaded from a checkpoint: keep its values
                     if cur.numel() != e - b:
                         raise ValueError(f"fused optimizer: loaded state '{k}' of parameter {i} has {cur.numel()} elements, its piece [{b}, {e}) has {e - b}")
-                    view.copy_(cur.to(device=device, dtype=torch.float32).reshape(-1))
+                    view.copy_(cur.to(device=device, dtype=view.dtype).reshape(-1))
                 elif k == "master":
                     view.copy_(p.detach().reshape(-1)[b:e])
                 st[k] = view
@@ -338,8 +376,9 @@ class _FusedOptimizer(torch.optim.Optimizer):
         return any(isinstance(v, torch.Tensor) and v.numel() and v.untyped_storage().data_ptr() == ptr for v in st.values())
 
     def load_state_dict(self, state_dict: dict) -> None:
-        """torch casts loaded state to the parameter's dtype; the state here is fp32 whatever the parameter is, so the saved
-        tensors are taken as they are (a torch.optim.AdamW checkpoint of fp32 parameters loads: same keys).
+        """torch casts loaded state to the parameter's dtype; the state here is fp32 (the moments: `state_dtype`) whatever the
+        parameter is, so the saved tensors are taken as they are (a torch.optim.AdamW checkpoint of fp32 parameters loads: same keys)
+        and converted to this optimizer's dtypes: bf16 moments widen exactly, fp32 moments go to bf16 by round-to-nearest-even, once.
         Sharded: a shard dictionary of the same world and rank, or an unsharded one from which this rank takes its ranges."""
         saved = state_dict.get("shard")
         here = self._shard or (0, 1)
@@ -357,10 +396,16 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 continue
             for k in self._state_keys + ("master",):
                 if k in src:
-                    self.state[p][k] = src[k].detach().to(device=p.device, dtype=torch.float32).clone()
+                    self.state[p][k] = src[k].detach().to(device=p.device, dtype=self._dtype_of(k)).clone()
             if "step" in src:
                 self.state[p]["step"] = torch.as_tensor(src["step"], dtype=torch.float32).detach().cpu().clone()
         self._flat, self._table, self._table_key = [], None, []
+        self._after_load()
+
+    def _after_load(self) -> None:
+        for group in self.param_groups:  # a dictionary saved before `seed` existed (or by torch.optim.AdamW) has none
+            if "seed" in self.defaults:
+                group.setdefault("seed", self.defaults["seed"])
 
     def _load_state_dict_sharded(self, state_dict: dict, pieces: bool) -> None:
         """Hyper-parameters through torch; of the state only the own ranges are brought to the device."""
@@ -375,10 +420,11 @@ class _FusedOptimizer(torch.optim.Optimizer):
             for k in self._state_keys + ("master",):
                 if k in src:
                     t = src[k].detach().reshape(-1)
-                    self.state[p][k] = (t if pieces else t[b:e]).to(device=p.device, dtype=torch.float32).clone()
+                    self.state[p][k] = (t if pieces else t[b:e]).to(device=p.device, dtype=self._dtype_of(k)).clone()
             if "step" in src:
                 self.state[p]["step"] = torch.as_tensor(src["step"], dtype=torch.float32).detach().cpu().clone()
         self._shard_flat, self._flat, self._table, self._table_key = {}, [], None, []
+        self._after_load()
 
     # ---- fp32 gradient accumulation ---------------------------------------------------------------------------------------
     def _grad_of(self, p: torch.Tensor) -> torch.Tensor | None:
@@ -585,10 +631,12 @@ class _FusedOptimizer(torch.optim.Optimizer):
             raise ValueError(f"fused optimizer: all parameters must live on one device (got {sorted(map(str, devices))})")
         self._ensure_state()
         everything = entries
+        ordinals = list(range(len(everything)))  # a parameter's index in param_groups order: what its random bits are keyed on
         if self._shard is not None:  # one segment per owned piece; `entries` = the parameters this rank owns a piece of
             mine = self._layout()[4]
             ranges = [mine[i] for i in range(len(everything)) if i in mine]
             entries = [e for i, e in enumerate(everything) if i in mine]
+            ordinals = [i for i in ordinals if i in mine]
         else:
             ranges = [(0, p.numel()) for p, _ in entries]
         table = (_lib.PrlOptimSegment * max(len(entries), 1))()
@@ -600,6 +648,16 @@ class _FusedOptimizer(torch.optim.Optimizer):
             seg.grad_dtype = _DTYPES[g.dtype] if g is not None else _DTYPES[p.dtype]
             if g is not None:
                 self._fill_state(seg, st)
+        if self._compact:  # the same entries with the rounding fields; step / lr / weight_decay are copied before every launch
+            self._compact_table = (_lib.PrlOptimCompactSegment * max(len(entries), 1))()
+            stochastic = self.param_rounding == "stochastic"
+            for seg, c, (p, _), (b, _e), ordinal in zip(table, self._compact_table, entries, ranges, ordinals):
+                for name, _t in _lib.PrlOptimSegment._fields_:
+                    setattr(c, name, getattr(seg, name))
+                c.state_dtype = _DTYPES[self.state_dtype]
+                sr = stochastic and p.dtype == torch.bfloat16 and not self._wants_master(p)
+                c.param_rounding = _lib.PRL_ROUND_STOCHASTIC if sr else _lib.PRL_ROUND_NEAREST
+                c.elem_offset, c.ordinal = b, ordinal
         self._norm_table = None
         if self._shard is not None and self.grad_accum_dtype is None:  # complete gradients on every rank: the norm reads them whole
             self._norm_table = (_lib.PrlOptimSegment * max(len(everything), 1))()
@@ -802,6 +860,10 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     def _launch(self, lib, table, n: int, record: int | None) -> None:
         """One call per run of consecutive groups that agree on the launch-level constants (betas, eps): normally one."""
+        if self._compact:
+            for seg, c in zip(table, self._compact_table):
+                c.step, c.lr, c.weight_decay = seg.step, seg.lr, seg.weight_decay
+            table = self._compact_table
         sizes = self._table_group_sizes  # the table's entries per group (sharded: the parameters this rank owns a piece of)
         keys = [self._launch_key(g) for g in self.param_groups]
         first, off = 0, 0
@@ -823,37 +885,50 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
 
 class FusedAdamW(_FusedOptimizer):
-    """`torch.optim.AdamW` (amsgrad off) as one fused launch per 32 parameters; fp32 state, optional fp32 master weights."""
+    """`torch.optim.AdamW` (amsgrad off) as one fused launch per 32 parameters; fp32 state, optional fp32 master weights.
+    `state_dtype=torch.bfloat16`: bf16 moments stored with stochastic rounding; `param_rounding="stochastic"`: a bf16 parameter
+    without a master copy is written with stochastic rounding; `seed` keys the random bits (module docstring)."""
 
     _state_keys = ("exp_avg", "exp_avg_sq")
 
     def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 master_weights: bool = True, grad_accum_dtype: torch.dtype | None = None, shard_group=None, shard: tuple[int, int] | None = None):
+                 master_weights: bool = True, grad_accum_dtype: torch.dtype | None = None, shard_group=None, shard: tuple[int, int] | None = None,
+                 state_dtype: torch.dtype | None = None, param_rounding: str = "nearest", seed: int = 0):
         _check_hyper(lr, betas, weight_decay, eps)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), master_weights, grad_accum_dtype, shard_group, shard)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, seed=seed), master_weights, grad_accum_dtype, shard_group,
+                         shard, state_dtype, param_rounding)
 
     def _launch_key(self, group):
-        return (float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]))
+        return (float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), int(group.get("seed", 0)))
 
     def _call(self, lib, table, n, key, record):
-        _lib.check(lib.prl_optim_adamw_step(table, n, key[0], key[1], key[2], record, self._stream()))
+        if self._compact:
+            _lib.check(lib.prl_optim_adamw_step_compact(table, n, key[0], key[1], key[2], key[3], record, self._stream()))
+        else:
+            _lib.check(lib.prl_optim_adamw_step(table, n, key[0], key[1], key[2], record, self._stream()))
 
 
 class FusedLion(_FusedOptimizer):
-    """The reference's `Lion` (pipelinerl/finetune/optim.py:48-112) as one fused launch per 32 parameters."""
+    """The reference's `Lion` (pipelinerl/finetune/optim.py:48-112) as one fused launch per 32 parameters.  `state_dtype`,
+    `param_rounding`, `seed`: compact state as in `FusedAdamW`."""
 
     _state_keys = ("exp_avg",)
 
     def __init__(self, params, lr: float = 1e-4, betas: tuple[float, float] = (0.9, 0.99), weight_decay: float = 0.0, master_weights: bool = True,
-                 grad_accum_dtype: torch.dtype | None = None, shard_group=None, shard: tuple[int, int] | None = None):
+                 grad_accum_dtype: torch.dtype | None = None, shard_group=None, shard: tuple[int, int] | None = None,
+                 state_dtype: torch.dtype | None = None, param_rounding: str = "nearest", seed: int = 0):
         _check_hyper(lr, betas, weight_decay)
-        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay), master_weights, grad_accum_dtype, shard_group, shard)
+        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay, seed=seed), master_weights, grad_accum_dtype, shard_group, shard,
+                         state_dtype, param_rounding)
 
     def _launch_key(self, group):
-        return (float(group["betas"][0]), float(group["betas"][1]))
+        return (float(group["betas"][0]), float(group["betas"][1]), int(group.get("seed", 0)))
 
     def _call(self, lib, table, n, key, record):
-        _lib.check(lib.prl_optim_lion_step(table, n, key[0], key[1], record, self._stream()))
+        if self._compact:
+            _lib.check(lib.prl_optim_lion_step_compact(table, n, key[0], key[1], key[2], record, self._stream()))
+        else:
+            _lib.check(lib.prl_optim_lion_step(table, n, key[0], key[1], record, self._stream()))
 
 
 class FusedAdafactor(_FusedOptimizer):
@@ -871,7 +946,10 @@ class FusedAdafactor(_FusedOptimizer):
 
     def __init__(self, params, lr: float = 1e-3, eps1: float = 1e-30, clip_threshold: float = 1.0, decay_rate: float = -0.8, weight_decay: float = 0.0,
                  master_weights: bool = True, grad_accum_dtype: torch.dtype | None = None, beta1=None, relative_step: bool = False,
-                 scale_parameter: bool = False, shard_group=None, shard: tuple[int, int] | None = None):
+                 scale_parameter: bool = False, shard_group=None, shard: tuple[int, int] | None = None, state_dtype: torch.dtype | None = None,
+                 param_rounding: str = "nearest", seed: int = 0):
+        if state_dtype not in (None, torch.float32) or param_rounding != "nearest" or seed != 0:
+            raise ValueError("FusedAdafactor: compact state (state_dtype, param_rounding, seed) is not built for Adafactor (its factored averages are tiny)")
         unsupported = [n for n, on in (("beta1", beta1 is not None), ("relative_step", relative_step), ("scale_parameter", scale_parameter)) if on]
         if unsupported:
             raise ValueError(f"FusedAdafactor: {', '.join(unsupported)} not supported (the fused step is the reference's rule: beta1=None, "
@@ -966,12 +1044,17 @@ class FusedAdafactor(_FusedOptimizer):
 
 
 def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weight_decay: float, grad_accum_dtype: torch.dtype | None = None,
-                  shard_group=None, shard: tuple[int, int] | None = None):
+                  shard_group=None, shard: tuple[int, int] | None = None, state_dtype: torch.dtype | None = None, param_rounding: str = "nearest",
+                  seed: int = 0):
     """The reference's dispatch (:25-45) with its names; "adamw_torch" and "lion" are the fused HIP steps, "adafactor_hip" is the
     fused HIP form of "adafactor" (which stays transformers' class).
     `grad_accum_dtype=torch.float32`: fp32 gradient accumulation (the fused steps only); `shard_group` / `shard`: state sharded over
-    the learner ranks ("adamw_torch" and "lion" only)."""
+    the learner ranks ("adamw_torch" and "lion" only); `state_dtype` / `param_rounding` / `seed`: compact state with stochastic rounding
+    ("adamw_torch" and "lion" only)."""
     grouped_params = get_grouped_params(model, weight_decay)
+    compact = dict(state_dtype=state_dtype, param_rounding=param_rounding, seed=seed)
+    if (state_dtype not in (None, torch.float32) or param_rounding != "nearest" or seed != 0) and name not in ("adamw_torch", "lion"):
+        raise ValueError(f'compact optimizer state (state_dtype, param_rounding, seed) needs "adamw_torch" or "lion", not "{name}"')
     if name == "adafactor_hip":
         return FusedAdafactor(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype, shard_group=shard_group, shard=shard)
     if grad_accum_dtype is not None and name not in ("adamw_torch", "lion"):
@@ -979,7 +1062,7 @@ def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weigh
     if (shard_group is not None or shard is not None) and name not in ("adamw_torch", "lion"):
         raise ValueError(f'sharded optimizer state needs a fused optimizer ("adamw_torch" or "lion"), not "{name}"')
     if name == "adamw_torch":
-        return FusedAdamW(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype, shard_group=shard_group, shard=shard)
+        return FusedAdamW(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype, shard_group=shard_group, shard=shard, **compact)
     if name == "adafactor":
         from transformers import Adafactor
 
@@ -991,5 +1074,5 @@ def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weigh
             raise ImportError(f'optimizer "cpuadam" needs the deepspeed package: {e}') from e
         return deepspeed.ops.adam.DeepSpeedCPUAdam(grouped_params, lr=learning_rate)
     if name == "lion":
-        return FusedLion(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype, shard_group=shard_group, shard=shard)
+        return FusedLion(grouped_params, lr=learning_rate, grad_accum_dtype=grad_accum_dtype, shard_group=shard_group, shard=shard, **compact)
     raise ValueError(f"Unknown optimizer: {name}")

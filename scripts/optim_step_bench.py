@@ -28,6 +28,18 @@ all three in ONE child process on the same gradients, HIP events around each rep
 both in ONE child process, alternating, HIP events around each boundary, 20 boundaries after warm-up, median [min, max].
 
     python scripts/optim_step_bench.py --mode adafactor --out profiles/adafactor_step_bench.json
+
+`--mode compact` times the AdamW STEP alone (`step()`, coefficient 1, no norm pass) with compact state against the fp32-state step, on the
+same parameters and gradients (the 7B list; each configuration has its own state):
+
+  fp32_state         FusedAdamW(master_weights=False)                                   (optim_step_kernel: 22 B per bf16 element)
+  fp32_state_master  FusedAdamW(master_weights=True)                                    (optim_step_kernel: 28 B)
+  compact            FusedAdamW(master_weights=False, state_dtype=torch.bfloat16, param_rounding="stochastic")
+                                                                                        (optim_step_compact_kernel: 14 B)
+
+all three in ONE child process, alternating, HIP events around each step, 20 steps after warm-up, median [min, max].
+
+    python scripts/optim_step_bench.py --mode compact --out profiles/optim_compact_step_bench.json
 """
 
 from __future__ import annotations
@@ -219,6 +231,96 @@ def run_adafactor(steps: int, warmup: int, max_norm: float) -> dict:
     return out
 
 
+COMPACT_CONFIGS = {
+    "fp32_state": dict(master_weights=False),
+    "fp32_state_master": dict(master_weights=True),
+    "compact": dict(master_weights=False, state_dtype="bf16", param_rounding="stochastic"),
+}
+
+
+def compact_step_bytes(p, kw) -> int:
+    """Algorithmic bytes of one AdamW step of one parameter: g, weights, m, v read; weights (+ the bf16 image under a master), m, v written."""
+    e, s = p.element_size(), (2 if kw.get("state_dtype") == "bf16" else 4)
+    master = kw["master_weights"] and e == 2
+    return p.numel() * (e + (4 if master else e) + 2 * s + (4 if master else 0) + e + 2 * s)
+
+
+def run_compact(steps: int, warmup: int) -> dict:
+    import torch
+
+    from pipelinerl_amd.finetune.optim import FusedAdamW
+    from pipelinerl_amd.weight_sync_probe import qwen25_shapes
+
+    dev = torch.device("cuda", 0)
+    shapes = qwen25_shapes("7b")
+    full = len(shapes)
+    free, _ = torch.cuda.mem_get_info(dev)
+
+    def need(shapes):  # parameters and gradients once, the state of every configuration (8 + 12 + 4 B per bf16 element)
+        total = 0
+        for name, shape in shapes:
+            n = 1
+            for d in shape:
+                n *= d
+            e = 4 if name == "lm_head.weight" else 2
+            total += n * (2 * e + 8 + (12 if e == 2 else 8) + 4)
+        return total
+
+    while need(shapes) > 0.85 * free:  # the largest prefix of the list that fits
+        shapes = shapes[:-1]
+    params = []
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for name, shape in shapes:
+        dtype = torch.float32 if name == "lm_head.weight" else torch.bfloat16
+        p = torch.nn.Parameter(torch.empty(shape, dtype=dtype, device=dev).normal_(0.0, 0.02, generator=gen))
+        p.grad = torch.empty(shape, dtype=dtype, device=dev).normal_(0.0, 1e-3, generator=gen)
+        params.append(p)
+    opts = {}
+    for name, kw in COMPACT_CONFIGS.items():
+        kw = dict(kw)
+        if kw.get("state_dtype") == "bf16":
+            kw["state_dtype"] = torch.bfloat16
+        opts[name] = FusedAdamW(params, lr=1e-6, **kw)
+    times = {k: [] for k in opts}
+    for k in range(warmup + steps):  # alternating: the three see the same clocks
+        for name, opt in opts.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            opt.step()
+            b.record()
+            b.synchronize()
+            if k >= warmup:
+                times[name].append(a.elapsed_time(b))
+    out = {"tensors": len(params), "of_tensors": full, "numel": sum(p.numel() for p in params), "steps": steps, "warmup": warmup, "results": {}}
+    for name, t in times.items():
+        med = statistics.median(t)
+        alg = sum(compact_step_bytes(p, COMPACT_CONFIGS[name]) for p in params)
+        gbs = alg / (med * 1e-3) / 1e9
+        state = sum(f.numel() * f.element_size() for f in opts[name]._flat)
+        out["results"][name] = {"median_ms": med, "min_ms": min(t), "max_ms": max(t), "algorithmic_bytes": alg, "achieved_gbs": gbs,
+                                "frac_of_peak": gbs / PEAK_GBS, "frac_of_copy_ceiling": gbs / COPY_CEILING_GBS, "state_bytes": state}
+    return out
+
+
+def main_compact(args) -> None:
+    cmd = [sys.executable, __file__, "--one", "compact", "--steps", str(args.steps), "--warmup", str(args.warmup)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
+    line = next((l for l in res.stdout.splitlines() if l.startswith("RESULT ")), None)
+    if res.returncode != 0 or line is None:
+        raise SystemExit(f"compact: exit status {res.returncode}\n{res.stdout[-2000:]}\n{res.stderr[-4000:]}")
+    report = json.loads(line[len("RESULT "):])
+    r = report["results"]
+    spread = r["fp32_state"]["max_ms"] - r["fp32_state"]["min_ms"]
+    report = {"workload": "Qwen2.5-7B parameter list, bf16 parameters and gradients, fp32 lm_head: the AdamW step alone", **report,
+              "spread_fp32_state_ms": spread, "compact_gain_ms": r["fp32_state"]["median_ms"] - r["compact"]["median_ms"],
+              "compact_is_not_slower_than_fp32_state": r["compact"]["median_ms"] <= r["fp32_state"]["median_ms"] + spread}
+    text = json.dumps(report, indent=1)
+    print(text)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(text + "\n")
+
+
 def main_adafactor(args) -> None:
     cmd = [sys.executable, __file__, "--one", "adafactor", "--steps", str(args.steps), "--warmup", str(args.warmup), "--max-norm", str(args.max_norm)]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
@@ -263,10 +365,16 @@ def main() -> None:
     ap.add_argument("--max-norm", type=float, default=0.3)
     ap.add_argument("--timeout", type=int, default=300, help="seconds per configuration")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--mode", choices=("boundary", "grad_accum", "adafactor"), default="boundary",
-                    help="what to time: the AdamW step boundary, the fp32 gradient fold, or the Adafactor boundary")
-    ap.add_argument("--one", choices=CONFIGS + ("grad_accum", "adafactor"), default=None, help="(child) run one configuration in this process")
+    ap.add_argument("--mode", choices=("boundary", "grad_accum", "adafactor", "compact"), default="boundary",
+                    help="what to time: the AdamW step boundary, the fp32 gradient fold, the Adafactor boundary, or the compact-state step")
+    ap.add_argument("--one", choices=CONFIGS + ("grad_accum", "adafactor", "compact"), default=None, help="(child) run one configuration in this process")
     args = ap.parse_args()
+    if args.one == "compact":
+        print("RESULT " + json.dumps(run_compact(args.steps, args.warmup)), flush=True)
+        return
+    if args.mode == "compact":
+        main_compact(args)
+        return
     if args.one == "grad_accum":
         print("RESULT " + json.dumps(run_grad_accum(args.steps, args.warmup)), flush=True)
         return

@@ -60,7 +60,7 @@
 extern "C" {
 #endif
 
-#define PRL_ABI_VERSION 18
+#define PRL_ABI_VERSION 19
 
 #define PRL_OK 0
 #define PRL_EINVAL (-22)   /* bad argument                                  */
@@ -716,6 +716,27 @@ typedef struct prl_accum_segment {
 } prl_accum_segment;
 int prl_optim_grad_accumulate(const prl_accum_segment* segments, int64_t n_segments,
                               int32_t overwrite, prl_stream_t stream);
+
+/* The same fold over EVERY rank's copy of a gradient piece in one pass (sharded gradients: the pieces an all-to-all
+ * delivered to their owner, rank r's copy `rank_stride_bytes` behind rank r - 1's):
+ *   overwrite == 0: acc[i] = (((acc[i] + g_0[i]) + g_1[i]) + ...) + g_{world-1}[i]
+ *   overwrite != 0: acc[i] = (((float)g_0[i] + g_1[i]) + ...) + g_{world-1}[i]       acc is not read
+ * one IEEE fp32 add per term in rank order, no scaling: bit for bit what `world` calls of prl_optim_grad_accumulate
+ * give, for 8 + world x itemsize bytes per element instead of world x (8 + itemsize).  `segments` is a HOST array of
+ * device pointers; `src == NULL` or `numel == 0` is skipped; multi-tensor launches of <= 64 segments, no atomics,
+ * nothing allocates or synchronises; arguments are validated before any device work (PRL_EINVAL names the segment):
+ * `world` in [1, PRL_ACCUM_RANKS_MAX_WORLD], `rank_stride_bytes` >= 0 and a multiple of 16 (so that every rank's copy
+ * has the alignment of rank 0's).  Pointers that are not 16-byte aligned take a scalar path. */
+#define PRL_ACCUM_RANKS_MAX_WORLD 64
+typedef struct prl_accum_ranks_segment {
+  const void* src;   /* rank 0's copy of this piece; rank r's copy is at (char*)src + r * rank_stride_bytes */
+  void* acc;         /* fp32 accumulator, numel elements */
+  int64_t numel;
+  int32_t src_dtype; /* PRL_DTYPE_BF16 or PRL_DTYPE_F32 */
+  int32_t reserved;  /* 0 */
+} prl_accum_ranks_segment;
+int prl_optim_grad_accumulate_ranks(const prl_accum_ranks_segment* segments, int64_t n_segments, int32_t world,
+                                    int64_t rank_stride_bytes, int32_t overwrite, prl_stream_t stream);
 
 /* ---- Adafactor step (the reference's get_optimizer("adafactor"): transformers' Adafactor with relative_step=False,
  * scale_parameter=False, beta1=None) ------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libprl.so"
 
-PRL_ABI_VERSION = 18
+PRL_ABI_VERSION = 19
 PRL_OK = 0
 PRL_EINVAL = -22
 PRL_ENOMEM = -12
@@ -132,6 +132,15 @@ class PrlAccumSegment(ctypes.Structure):
     _fields_ = [("grad", c_void_p), ("acc", c_void_p), ("numel", c_int64), ("grad_dtype", c_int32), ("reserved", c_int32)]
 
 
+PRL_ACCUM_RANKS_MAX_WORLD = 64  # the largest `world` of prl_optim_grad_accumulate_ranks
+
+
+class PrlAccumRanksSegment(ctypes.Structure):
+    """Mirror of `struct prl_accum_ranks_segment` (include/prl.h)."""
+
+    _fields_ = [("src", c_void_p), ("acc", c_void_p), ("numel", c_int64), ("src_dtype", c_int32), ("reserved", c_int32)]
+
+
 class PrlOptimSegment(ctypes.Structure):
     """Mirror of `struct prl_optim_segment` (include/prl.h)."""
 
@@ -239,6 +248,7 @@ PROTOTYPES: dict[str, tuple] = {
     "prl_optim_adamw_step_compact": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_uint64, _P, _P]),
     "prl_optim_lion_step_compact": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, c_uint64, _P, _P]),
     "prl_optim_grad_accumulate": (c_int32, [_P, c_int64, c_int32, _P]),
+    "prl_optim_grad_accumulate_ranks": (c_int32, [_P, c_int64, c_int32, c_int64, c_int32, _P]),
     "prl_adafactor_workspace_bytes": (c_int32, [_P, c_int64, POINTER(c_size_t)]),
     "prl_adafactor_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, c_size_t, _P]),
     "prl_adafactor_geometry": (c_int32, [POINTER(c_int64)] * 4),

@@ -1,6 +1,6 @@
 // Learner-step boundary: gradient norm + clip coefficient, then the AdamW / Lion update of EVERY parameter,
 // as multi-tensor launches (one per <= 64 gradients for the norm, per <= 32 parameters for the step); and, in front of it, the
-// fold of every micro-batch's gradients into fp32 accumulators (one launch per <= 64 gradients).
+// fold of every micro-batch's gradients into fp32 accumulators (one launch per <= 64 gradients), one rank's or every rank's copy at once.
 //
 // Replaces `torch.nn.utils.clip_grad_norm_` -> `float(gn)` -> `optimizer.step()` of
 // pipelinerl/finetune_loop.py:738-744 (a multi-pass foreach norm, a host sync, an in-place rescale of every
@@ -27,7 +27,7 @@ using namespace prl::optim_io;  // load8 / store8 / load1 / store1 / owner, kGro
 constexpr int kBlock = 256;
 constexpr int64_t kChunk = 16 << 10;       // elements per workgroup: 8 iterations of 256 lanes x 8 elements
 constexpr int kNormSegs = 64;              // per launch: 64 x 21 B of kernel arguments
-constexpr int kAccumSegs = 64;             // per launch: 64 x 29 B
+constexpr int kAccumSegs = 64;             // per launch: 64 x 29 B (both fold kernels)
 constexpr int kStepSegs = 32;              // per launch: 32 x 90 B (64 would not fit 4 KB of kernel arguments)
 constexpr int kFinalBlock = 1024;
 
@@ -275,6 +275,81 @@ __global__ __launch_bounds__(kBlock) void grad_accumulate_kernel(const AccumTabl
   else chunk_accumulate<false, OVERWRITE>(static_cast<const float*>(tab.grad[s]) + begin, acc, len);
 }
 
+// The same fold over the `world` ranks' copies of one piece at once (sharded gradients: what an all-to-all delivered): rank r's copy
+// stands `stride` bytes behind rank r - 1's.  acc = (((acc + g_0) + g_1) + ...) + g_{world-1}, the adds in rank order, so the result is
+// what `world` calls of the kernel above give, bit for bit - for 8 + world x itemsize bytes per element instead of world x (8 + itemsize).
+// Four ranks' loads are issued before their adds (a remainder loop takes world mod 4); `stride` is a multiple of 16, so every rank's
+// copy has the alignment of rank 0's.
+struct AccumRanksTable {
+  const void* src[kAccumSegs];
+  float* acc[kAccumSegs];
+  int64_t numel[kAccumSegs];
+  int32_t first_chunk[kAccumSegs + 1];
+  uint8_t bf16[kAccumSegs];
+  int32_t n;
+  int32_t world;
+  int64_t stride;  // bytes between two ranks' copies
+};
+
+__device__ __forceinline__ const void* rank_copy(const void* src, int64_t stride, int r) { return static_cast<const char*>(src) + int64_t(r) * stride; }
+
+template <bool GB, bool OVERWRITE>
+__device__ __forceinline__ void chunk_accumulate_ranks(const void* src, int64_t stride, int world, float* acc, int64_t len) {
+  int64_t done = 0;
+  if (aligned16_dev(src) && aligned16_dev(acc)) {
+    const int64_t ngroups = len / kGroup;
+    for (int64_t q = threadIdx.x; q < ngroups; q += kBlock) {
+      const int64_t i = q * kGroup;
+      float a[kGroup];
+      int r = 0;
+      if constexpr (OVERWRITE) {
+        float g[kGroup];
+        load8<GB>(src, i, g);
+#pragma unroll
+        for (int k = 0; k < kGroup; ++k) a[k] = prl_grad_accum_first(g[k]);
+        r = 1;
+      } else {
+        load8<false>(acc, i, a);
+      }
+      for (; r + 4 <= world; r += 4) {
+        float g0[kGroup], g1[kGroup], g2[kGroup], g3[kGroup];
+        load8<GB>(rank_copy(src, stride, r), i, g0);
+        load8<GB>(rank_copy(src, stride, r + 1), i, g1);
+        load8<GB>(rank_copy(src, stride, r + 2), i, g2);
+        load8<GB>(rank_copy(src, stride, r + 3), i, g3);
+#pragma unroll
+        for (int k = 0; k < kGroup; ++k)
+          a[k] = prl_grad_accum_add(prl_grad_accum_add(prl_grad_accum_add(prl_grad_accum_add(a[k], g0[k]), g1[k]), g2[k]), g3[k]);
+      }
+      for (; r < world; ++r) {
+        float g[kGroup];
+        load8<GB>(rank_copy(src, stride, r), i, g);
+#pragma unroll
+        for (int k = 0; k < kGroup; ++k) a[k] = prl_grad_accum_add(a[k], g[k]);
+      }
+      store8_stream(acc, i, a);  // read next by the following fold, a whole backward later
+    }
+    done = ngroups * kGroup;
+  }
+  for (int64_t i = done + threadIdx.x; i < len; i += kBlock) {  // tail, or a whole unaligned view
+    float a = OVERWRITE ? prl_grad_accum_first(load1<GB>(src, i)) : acc[i];
+    for (int r = OVERWRITE ? 1 : 0; r < world; ++r) a = prl_grad_accum_add(a, load1<GB>(rank_copy(src, stride, r), i));
+    acc[i] = a;
+  }
+}
+
+template <bool OVERWRITE>
+__global__ __launch_bounds__(kBlock) void grad_accumulate_ranks_kernel(const AccumRanksTable tab) {
+  const int chunk = blockIdx.x;
+  const int s = owner(tab.first_chunk, tab.n, chunk);
+  const int64_t begin = int64_t(chunk - tab.first_chunk[s]) * kChunk;
+  const int64_t left = tab.numel[s] - begin;
+  const int64_t len = left < kChunk ? left : kChunk;
+  float* acc = tab.acc[s] + begin;
+  if (tab.bf16[s]) chunk_accumulate_ranks<true, OVERWRITE>(static_cast<const uint16_t*>(tab.src[s]) + begin, tab.stride, tab.world, acc, len);
+  else chunk_accumulate_ranks<false, OVERWRITE>(static_cast<const float*>(tab.src[s]) + begin, tab.stride, tab.world, acc, len);
+}
+
 int64_t chunks_of(int64_t numel) { return (numel + kChunk - 1) / kChunk; }
 bool live(const prl_optim_segment& s) { return s.grad != nullptr && s.numel > 0; }
 
@@ -460,6 +535,49 @@ extern "C" int prl_optim_grad_accumulate(const prl_accum_segment* segments, int6
     if (overwrite) hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3(unsigned(chunks)), dim3(kBlock), 0, st, tab);
     else hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3(unsigned(chunks)), dim3(kBlock), 0, st, tab);
     PRL_LAUNCH_CHECK("grad_accumulate_kernel");
+  }
+  return PRL_OK;
+}
+
+extern "C" int prl_optim_grad_accumulate_ranks(const prl_accum_ranks_segment* segments, int64_t n_segments, int32_t world,
+                                               int64_t rank_stride_bytes, int32_t overwrite, prl_stream_t stream) {
+  PRL_CHECK_ARG(n_segments >= 0, "negative segment count");
+  PRL_CHECK_ARG(n_segments == 0 || segments != nullptr, "null segment table with %lld segments", (long long)n_segments);
+  PRL_CHECK_ARG(world >= 1 && world <= PRL_ACCUM_RANKS_MAX_WORLD, "world %d outside [1, %d]", world, PRL_ACCUM_RANKS_MAX_WORLD);
+  PRL_CHECK_ARG(rank_stride_bytes >= 0 && rank_stride_bytes % 16 == 0, "rank_stride_bytes %lld is negative or not a multiple of 16",
+                (long long)rank_stride_bytes);
+  for (int64_t i = 0; i < n_segments; ++i) {
+    const prl_accum_ranks_segment& s = segments[i];
+    PRL_CHECK_ARG(s.numel >= 0, "segment %lld: negative numel %lld", (long long)i, (long long)s.numel);
+    PRL_CHECK_ARG(chunks_of(s.numel) < (int64_t(1) << 30), "segment %lld: %lld elements are too many for one launch", (long long)i, (long long)s.numel);
+    PRL_CHECK_ARG(s.src_dtype == PRL_DTYPE_F32 || s.src_dtype == PRL_DTYPE_BF16, "segment %lld: unknown src_dtype %d", (long long)i, s.src_dtype);
+    PRL_CHECK_ARG(s.src == nullptr || s.numel == 0 || s.acc != nullptr, "segment %lld: null acc", (long long)i);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int64_t i = 0;
+  while (i < n_segments) {
+    AccumRanksTable tab;
+    tab.n = 0;
+    tab.world = world;
+    tab.stride = rank_stride_bytes;
+    tab.first_chunk[0] = 0;
+    int64_t chunks = 0;
+    for (; i < n_segments && tab.n < kAccumSegs; ++i) {
+      const prl_accum_ranks_segment& s = segments[i];
+      if (s.src == nullptr || s.numel == 0) continue;
+      const int64_t c = chunks_of(s.numel);
+      if (chunks + c > (int64_t(1) << 30)) break;  // keep the grid and the prefix sums in int32
+      tab.src[tab.n] = s.src;
+      tab.acc[tab.n] = static_cast<float*>(s.acc);
+      tab.numel[tab.n] = s.numel;
+      tab.bf16[tab.n] = s.src_dtype == PRL_DTYPE_BF16;
+      chunks += c;
+      tab.first_chunk[++tab.n] = int32_t(chunks);
+    }
+    if (tab.n == 0) break;  // only skipped segments were left
+    if (overwrite) hipLaunchKernelGGL(grad_accumulate_ranks_kernel<true>, dim3(unsigned(chunks)), dim3(kBlock), 0, st, tab);
+    else hipLaunchKernelGGL(grad_accumulate_ranks_kernel<false>, dim3(unsigned(chunks)), dim3(kBlock), 0, st, tab);
+    PRL_LAUNCH_CHECK("grad_accumulate_ranks_kernel");
   }
   return PRL_OK;
 }

@@ -40,6 +40,22 @@ With `shard=` there is no group to call: the caller moves the data between the h
 stand in for every rank.  `state_dict()` is this rank's shard plus the partition; `full_state_dict()` gathers an unsharded
 dictionary on rank 0, and an unsharded dictionary loads into shards (each rank takes its ranges).
 
+Sharded gradients (ZeRO-2; `shard_grads=True` on top of sharded state with `grad_accum_dtype=torch.float32`): the flat accumulator
+above is `world x shard_len` floats on every rank and is reduced once per step.  With the option a rank keeps the accumulator of its
+own range only (`shard_len` floats, views for the owned pieces) and every micro-batch's gradients travel to their owners at once, in
+bounded buckets: bucket k is elements `[k B, min((k + 1) B, shard_len))` of EVERY rank's range (`bucket_elems`, `plan_buckets`; B a
+multiple of 16 elements such that one destination's pieces of one bucket - each in its gradient's own dtype at a 16-byte aligned
+offset, a "slot" - never exceed `exchange_bucket_bytes`).  `accumulate_grads()` becomes a COLLECTIVE: per bucket it gathers this
+micro-batch's pieces into a send buffer of `world` slots (`prl_bucket_gather`; a parameter without a gradient here travels as +0.0),
+exchanges slot d with rank d (`all_to_all_single`, RCCL and gloo alike) and folds the `world` received copies of the own pieces into the
+accumulator in rank order in one pass (`prl_optim_grad_accumulate_ranks`).  `reduce_accumulated()` then moves nothing: it divides the
+own range by the world size.  The weight exchange after the step runs bucket by bucket through the same two buffers (`world x slot`
+bytes each, allocated once) instead of a whole-model receive buffer; the bytes that arrive are the same.  Per rank and micro-batch
+`(world - 1) / world` of the gradient bytes are sent - `world`-fold the traffic of one reduction per step when there are `world`
+micro-batches, the price of the memory.  Everything is stream-ordered on the current stream and single-buffered; overlapping a bucket's
+exchange with the next one's gather is not built.  With `shard=` the halves are `n_grad_buckets`, `pack_grad_bucket`,
+`fold_grad_bucket`, `finish_grad_fold` and `pack_shard_bucket` / `unpack_shard_bucket`.
+
 Gradient accumulation (`grad_accum_dtype=torch.float32`): autograd sums the micro-batch gradients into `p.grad` in the
 parameter's dtype, and a bf16 running sum drops every term below half an ulp of it - after 256 equal terms all of the next one.
 The reference accumulates in fp32 (FSDP `param_dtype / reduce_dtype: fp32`, DeepSpeed's fp32 gradient partitions).  With the
@@ -122,6 +138,44 @@ def plan_shards(numels, world: int, slot: int = _SLOT) -> list[list[tuple[int, i
     return plan
 
 
+def bucket_elems(exchange_bucket_bytes: int, widest: int = 4, slot: int = _SLOT) -> int:
+    """B of the bucketed exchange: the largest multiple of `slot` elements whose pieces fit `exchange_bucket_bytes` when every element
+    is `widest` bytes.  (Pieces begin on slot boundaries of the element space and a slot of elements is a multiple of 16 bytes, so the
+    16-byte padding of the pieces of one bucket stays inside `B x widest` bytes.)"""
+    if isinstance(exchange_bucket_bytes, bool) or not isinstance(exchange_bucket_bytes, int) or exchange_bucket_bytes < slot * 4:
+        raise ValueError(f"fused optimizer: exchange_bucket_bytes must be an int of at least {slot * 4} bytes (one slot of fp32 elements), got {exchange_bucket_bytes!r}")
+    return exchange_bucket_bytes // (slot * widest) * slot
+
+
+def plan_buckets(numels, itemsizes, world: int, bucket: int, slot: int = _SLOT):
+    """The bucketed exchange of sharded gradients / weights: `(n_buckets, slot_bytes, pieces)`.  Bucket k covers elements
+    `[k bucket, min((k + 1) bucket, shard_len))` of every rank's range of the padded element space (`shard_layout`);
+    `pieces[k][d]` lists what of it belongs to rank d as `(param_index, begin, end, byte_offset)`: element range inside the parameter
+    and where the piece stands in the slot - pieces in order, each at a 16-byte aligned offset, `itemsizes[param_index]` bytes per
+    element (the layout rule of the whole-buffer weight exchange).  `slot_bytes` is the largest slot, at least 16."""
+    if bucket < slot or bucket % slot:
+        raise ValueError(f"plan_buckets: bucket ({bucket}) must be a positive multiple of the slot ({slot})")
+    offsets, shard_len = shard_layout(numels, world, slot)
+    n_buckets = max(1, -(-shard_len // bucket))
+    pieces = [[[] for _ in range(world)] for _ in range(n_buckets)]
+    slot_bytes = 16
+    for d in range(world):
+        i = 0
+        for k in range(n_buckets):
+            lo, hi = d * shard_len + k * bucket, d * shard_len + min((k + 1) * bucket, shard_len)
+            while i < len(numels) and offsets[i] + int(numels[i]) <= lo:
+                i += 1
+            j, at = i, 0
+            while j < len(numels) and offsets[j] < hi:
+                b, e = max(offsets[j], lo) - offsets[j], min(offsets[j] + int(numels[j]), hi) - offsets[j]
+                if e > b:
+                    pieces[k][d].append((j, b, e, at))
+                    at += -(-(e - b) * itemsizes[j] // 16) * 16
+                j += 1
+            slot_bytes = max(slot_bytes, at)
+    return n_buckets, slot_bytes, pieces
+
+
 def _resolve_shard(shard_group, shard) -> tuple[int, int] | None:
     """(rank, world) of the sharded state, None for a world of one (today's unsharded behaviour)."""
     if shard_group is not None and shard is not None:
@@ -201,9 +255,15 @@ class _FusedOptimizer(torch.optim.Optimizer):
     _segment_type = _lib.PrlOptimSegment  # what `_launch` hands to `_call`
 
     def __init__(self, params: Iterable, defaults: dict[str, Any], master_weights: bool, grad_accum_dtype: torch.dtype | None = None,
-                 shard_group=None, shard: tuple[int, int] | None = None, state_dtype: torch.dtype | None = None, param_rounding: str = "nearest"):
+                 shard_group=None, shard: tuple[int, int] | None = None, state_dtype: torch.dtype | None = None, param_rounding: str = "nearest",
+                 shard_grads: bool = False, exchange_bucket_bytes: int = 64 << 20):
         if grad_accum_dtype not in (None, torch.float32):
             raise ValueError(f"fused optimizer: grad_accum_dtype must be None or torch.float32 (got {grad_accum_dtype})")
+        bucket_elems(exchange_bucket_bytes)  # (raises below one slot)
+        if shard_grads and grad_accum_dtype != torch.float32:
+            raise ValueError("fused optimizer: shard_grads=True shards the fp32 gradient accumulators: it needs grad_accum_dtype=torch.float32")
+        if shard_grads and shard_group is None and shard is None:
+            raise ValueError("fused optimizer: shard_grads=True needs sharded state (shard_group= or shard=)")
         self.state_dtype = _check_compact(state_dtype, param_rounding, defaults.get("seed", 0))
         self.param_rounding = param_rounding
         self._compact = self.state_dtype != torch.float32 or param_rounding != "nearest"  # the step goes through the compact entry points
@@ -212,6 +272,10 @@ class _FusedOptimizer(torch.optim.Optimizer):
             self._segment_type = _lib.PrlOptimCompactSegment
         self._shard = _resolve_shard(shard_group, shard)  # (rank, world), world > 1; None: unsharded
         self._shard_group = shard_group if self._shard is not None else None
+        self.shard_grads = bool(shard_grads) and self._shard is not None  # (a world of one: today's unsharded behaviour)
+        self.exchange_bucket_bytes = exchange_bucket_bytes
+        self._gx = None                           # sharded gradients: the bucket plan and the two exchange buffers
+        self._folded = False                      # sharded gradients: a micro-batch was folded since the last step / zero_grad
         super().__init__(params, defaults)
         self._lay = None                          # sharded: (numels, params, offsets, shard_len, {param index: (begin, end)})
         self._shard_flat: dict[str, torch.Tensor] = {}  # sharded: state key -> flat buffer of shard_len floats
@@ -304,7 +368,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
             if rank == 0:  # a parameter without elements has no piece; its step count lives on rank 0, so that the gathered state is complete
                 mine.update({i: (0, 0) for i, n in enumerate(numels) if n == 0})
             self._lay = (numels, params, offsets, shard_len, mine)
-            self._pub = self._pub_tables = None
+            self._pub = self._pub_tables = self._gx = None
         return self._lay
 
     @property
@@ -486,12 +550,18 @@ class _FusedOptimizer(torch.optim.Optimizer):
         if self._acc_flat is not None:
             self._layout()  # (raises when the parameter list changed)
             return
-        _, params, offsets, shard_len, _ = self._layout()
+        _, params, offsets, shard_len, mine = self._layout()
         if not params:
             return
         devices = {p.device for p in params}
         if len(devices) > 1:
             raise ValueError(f"fused optimizer: all parameters must live on one device (got {sorted(map(str, devices))})")
+        if self.shard_grads:  # this rank's range only; an owned piece's view is 1-D, its elements [begin, end) of the parameter
+            lo = self._shard[0] * shard_len
+            flat = torch.zeros(shard_len, dtype=torch.float32, device=params[0].device)
+            self._acc_flat = flat
+            self._acc = {params[i]: flat[offsets[i] + b - lo:offsets[i] + e - lo] for i, (b, e) in sorted(mine.items())}
+            return
         flat = torch.zeros(self._shard[1] * shard_len, dtype=torch.float32, device=params[0].device)
         self._acc_flat, self._acc = flat, {p: flat[off:off + p.numel()].view(p.shape) for p, off in zip(params, offsets)}
 
@@ -503,6 +573,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
         (`set_to_none=False`: zeroed in place).  fp32 gradients are left alone: they already accumulate in fp32."""
         if self.grad_accum_dtype is None:
             raise RuntimeError("fused optimizer: accumulate_grads() needs grad_accum_dtype=torch.float32")
+        if self.shard_grads:
+            return self._accumulate_grads_sharded(set_to_none)
         todo = [p for group in self.param_groups for p in group["params"] if self._unfolded(p)]
         if not todo:
             return
@@ -537,6 +609,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
         if self.grad_accum_dtype is None:
             raise RuntimeError("fused optimizer: reduce_accumulated() needs grad_accum_dtype=torch.float32")
+        if self.shard_grads:
+            return self._reduce_sharded_grads()
         if self._shard is not None:
             return self._reduce_accumulated_sharded(group)
         if not (dist.is_available() and dist.is_initialized()):
@@ -586,6 +660,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         slot that received nothing zeroed, ready to be summed over the ranks."""
         if self._shard is None or self.grad_accum_dtype is None:
             raise RuntimeError("fused optimizer: prepare_reduce() belongs to sharded state with grad_accum_dtype=torch.float32")
+        self._no_whole_buffer("prepare_reduce() / finish_reduce()", "pack_grad_bucket(k) / fold_grad_bucket(k, received) / finish_grad_fold() after every backward")
         self._check_all_folded()
         self._ensure_accumulators()
         for p, view in self._acc.items():
@@ -597,6 +672,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def finish_reduce(self, owned: torch.Tensor | None = None) -> None:
         """Second half: `owned` = the sum over the ranks of this rank's range (None: it already stands in the accumulator); the
         range is divided by the world size and every slot counts as having a gradient, so the ranks take identical steps."""
+        self._no_whole_buffer("prepare_reduce() / finish_reduce()", "pack_grad_bucket(k) / fold_grad_bucket(k, received) / finish_grad_fold() after every backward")
         rank, world = self._shard
         shard_len = self._layout()[3]
         mine = self._acc_flat[rank * shard_len:(rank + 1) * shard_len]
@@ -612,6 +688,192 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._acc_filled.clear()
         self._acc_zeroed.clear()
         self._reduced = False
+        self._folded = False
+
+    # ---- sharded gradients (ZeRO-2) ------------------------------------------------------------------------------------------
+    def _no_whole_buffer(self, what: str, instead: str) -> None:
+        if self.shard_grads:
+            raise RuntimeError(f"fused optimizer: {what} move whole buffers, which shard_grads=True does not allocate; use {instead}")
+
+    @staticmethod
+    def _grad_dtype(p: torch.Tensor) -> torch.dtype:
+        """The dtype a parameter's gradient travels in: a static rule, so that a rank without the gradient lays its zeros out alike."""
+        return getattr(p, "grad_dtype", None) or p.dtype
+
+    def _exchange(self) -> dict:
+        """The bucket plan (gradient pieces in the gradient's dtype, weight pieces in the parameter's; one B for both) and the two
+        buffers of `world x slot` bytes that both exchanges go through.  Allocated once."""
+        numels, params, offsets, shard_len, _ = self._layout()
+        if self._gx is None:
+            if not params:
+                raise ValueError("fused optimizer: no parameters")
+            devices = {p.device for p in params}
+            if len(devices) > 1:
+                raise ValueError(f"fused optimizer: all parameters must live on one device (got {sorted(map(str, devices))})")
+            _lib.require_device(*params)
+            world = self._shard[1]
+            g_sizes = [torch.empty((), dtype=self._grad_dtype(p)).element_size() for p in params]
+            w_sizes = [p.element_size() for p in params]
+            bucket = bucket_elems(self.exchange_bucket_bytes, max(g_sizes + w_sizes))
+            n, g_slot, g_pieces = plan_buckets(numels, g_sizes, world, bucket)
+            _, w_slot, w_pieces = plan_buckets(numels, w_sizes, world, bucket)
+            slot = max(g_slot, w_slot)
+            device = params[0].device
+            self._gx = {"bucket": bucket, "n": n, "slot": slot, "grad": g_pieces, "weight": w_pieces, "g_sizes": g_sizes,
+                        "send": torch.zeros(world * slot, dtype=torch.uint8, device=device), "recv": torch.zeros(world * slot, dtype=torch.uint8, device=device)}
+        return self._gx
+
+    def n_grad_buckets(self) -> int:
+        """Sharded gradients: the number of buckets one micro-batch's gradients (and the weights after the step) travel in."""
+        if not self.shard_grads:
+            raise RuntimeError("fused optimizer: n_grad_buckets() belongs to shard_grads=True")
+        return self._exchange()["n"]
+
+    @torch.no_grad()
+    def pack_grad_bucket(self, k: int) -> torch.Tensor:
+        """Sharded gradients, first half of a bucket's fold: this rank's send buffer for bucket `k` (uint8, `world` slots; slot d holds
+        this micro-batch's gradients of rank d's pieces of the bucket, +0.0 where a parameter has no gradient here).  The buffer is
+        reused by the next call: move it on (or copy it) first."""
+        if not self.shard_grads:
+            raise RuntimeError("fused optimizer: pack_grad_bucket() belongs to shard_grads=True")
+        gx = self._exchange()
+        params = self._layout()[1]
+        if not 0 <= k < gx["n"]:
+            raise IndexError(f"fused optimizer: bucket {k} of {gx['n']}")
+        if k == 0:  # once per micro-batch: the gradients that take part, checked
+            present = [self._unfolded(p) for p in params]
+            for p, here in zip(params, present):
+                if here:
+                    self._check_tensor(p, p.grad)
+                    if p.grad.dtype != self._grad_dtype(p):
+                        raise TypeError(f"fused optimizer: a gradient of dtype {p.grad.dtype} where {self._grad_dtype(p)} travels (set p.grad_dtype on every rank)")
+            gx["present"] = present
+        present, slot, send = gx["present"], gx["slot"], gx["send"]
+        pieces = [(d, piece) for d, dest in enumerate(gx["grad"][k]) for piece in dest]
+        live = [(d, piece) for d, piece in pieces if present[piece[0]]]
+        if len(live) < len(pieces):
+            send.zero_()  # what is absent here travels as +0.0
+        table = (_lib.PrlSegment * max(len(live), 1))()
+        for seg, (d, (i, b, e, at)) in zip(table, live):
+            isz = gx["g_sizes"][i]
+            seg.tensor, seg.bucket_offset, seg.nbytes = params[i].grad.data_ptr() + b * isz, d * slot + at, (e - b) * isz
+        _lib.check(_lib.load().prl_bucket_gather(send.data_ptr(), send.numel(), table, len(live), _lib.current_stream_ptr(send.device)))
+        return send
+
+    @torch.no_grad()
+    def fold_grad_bucket(self, k: int, received: torch.Tensor) -> None:
+        """Second half: `received` is `world x slot` bytes, slot r = what rank r packed for THIS rank in bucket `k`; the `world` copies
+        of every own piece are folded into its accumulator in rank order by one call (overwriting on the first micro-batch since the
+        last step / `zero_grad()`)."""
+        if not self.shard_grads:
+            raise RuntimeError("fused optimizer: fold_grad_bucket() belongs to shard_grads=True")
+        gx = self._exchange()
+        (rank, world), slot = self._shard, gx["slot"]
+        if not 0 <= k < gx["n"]:
+            raise IndexError(f"fused optimizer: bucket {k} of {gx['n']}")
+        if received.dtype != torch.uint8 or received.numel() != world * slot or not received.is_contiguous():
+            raise ValueError(f"fused optimizer: fold_grad_bucket() takes {world} x {slot} contiguous bytes")
+        _lib.require_device(received)
+        self._ensure_accumulators()
+        _, params, offsets, shard_len, _ = self._layout()
+        mine = gx["grad"][k][rank]
+        table = (_lib.PrlAccumRanksSegment * max(len(mine), 1))()
+        base = self._acc_flat.data_ptr() - 4 * rank * shard_len
+        for seg, (i, b, e, at) in zip(table, mine):
+            seg.src, seg.acc, seg.numel = received.data_ptr() + at, base + 4 * (offsets[i] + b), e - b
+            seg.src_dtype = _DTYPES[self._grad_dtype(params[i])]
+        _lib.check(_lib.load().prl_optim_grad_accumulate_ranks(table, len(mine), world, slot, int(not self._folded), _lib.current_stream_ptr(received.device)))
+
+    @torch.no_grad()
+    def finish_grad_fold(self, set_to_none: bool = True) -> None:
+        """Closes a micro-batch after its last bucket: clears `p.grad` (`set_to_none=False`: zeroed in place) and marks every own
+        accumulator filled, so that the next micro-batch adds."""
+        if not self.shard_grads:
+            raise RuntimeError("fused optimizer: finish_grad_fold() belongs to shard_grads=True")
+        self._ensure_accumulators()
+        self._folded = True
+        self._acc_filled.update(self._acc)
+        for p in self._layout()[1]:
+            if p.grad is None:
+                continue
+            if set_to_none:
+                p.grad = None  # (freed in stream order: the gathers above have been enqueued)
+                self._acc_zeroed.pop(p, None)
+            elif self._unfolded(p):
+                p.grad.zero_()
+                self._acc_zeroed[p] = (p.grad, p.grad._version)
+
+    def _accumulate_grads_sharded(self, set_to_none: bool) -> None:
+        """`accumulate_grads()` with sharded gradients: a COLLECTIVE.  Every rank of the group calls it once per micro-batch, also a rank
+        that has nothing to fold (its zeros are what the owners add) - the sentinel batches of the learner steps already make the
+        ranks run equal numbers of forward / backward passes.  Per bucket: gather, `all_to_all_single` (slot d goes to rank d; RCCL
+        and gloo alike), one fold of the `world` received copies.  Stream-ordered on the current stream and single-buffered: the next
+        bucket's gather waits for this bucket's exchange (overlapping the two on a second buffer is a later step)."""
+        import torch.distributed as dist
+
+        if self._shard_group is None:
+            raise RuntimeError("fused optimizer: shard= has no group to exchange the buckets over; move the data between pack_grad_bucket(k) and "
+                               "fold_grad_bucket(k, received), then finish_grad_fold()")
+        if dist.get_world_size(self._shard_group) != self._shard[1]:
+            raise RuntimeError(f"fused optimizer: the state is sharded over {self._shard[1]} ranks, the group has {dist.get_world_size(self._shard_group)}")
+        recv = self._exchange()["recv"]
+        for k in range(self.n_grad_buckets()):
+            send = self.pack_grad_bucket(k)
+            dist.all_to_all_single(recv, send, group=self._shard_group)
+            self.fold_grad_bucket(k, recv)
+        self.finish_grad_fold(set_to_none)
+
+    def _reduce_sharded_grads(self) -> None:
+        """`reduce_accumulated()` with sharded gradients moves no data (the owners already hold the sums): the own range is divided by
+        the world size and the step counts as reduced.  Nothing folded since the last step: the gradients are zero."""
+        self._check_all_folded()
+        self._ensure_accumulators()
+        if self._acc_flat is None:
+            return
+        if not self._folded:
+            self._acc_flat.zero_()
+            self._acc_filled.update(self._acc)
+        self._acc_flat.div_(self._shard[1])
+        self._reduced = True
+
+    @torch.no_grad()
+    def pack_shard_bucket(self, k: int) -> torch.Tensor:
+        """Sharded gradients, the weight exchange bucket by bucket: this rank's pieces of bucket `k` of the parameters, as they stand,
+        packed into the first slot of the send buffer (uint8, `slot` bytes, the same size on every rank)."""
+        if not self.shard_grads:
+            raise RuntimeError("fused optimizer: pack_shard_bucket() belongs to shard_grads=True")
+        gx = self._exchange()
+        params, slot = self._layout()[1], gx["slot"]
+        if not 0 <= k < gx["n"]:
+            raise IndexError(f"fused optimizer: bucket {k} of {gx['n']}")
+        mine = gx["weight"][k][self._shard[0]]
+        table = (_lib.PrlSegment * max(len(mine), 1))()
+        for seg, (i, b, e, at) in zip(table, mine):
+            isz = params[i].element_size()
+            seg.tensor, seg.bucket_offset, seg.nbytes = params[i].data_ptr() + b * isz, at, (e - b) * isz
+        send = gx["send"][:slot]
+        _lib.check(_lib.load().prl_bucket_gather(send.data_ptr(), slot, table, len(mine), _lib.current_stream_ptr(send.device)))
+        return send
+
+    @torch.no_grad()
+    def unpack_shard_bucket(self, k: int, gathered: torch.Tensor) -> None:
+        """`gathered`: every rank's `pack_shard_bucket(k)` in rank order (world x slot bytes); the other ranks' pieces are written into
+        the parameters, the own ones are already there."""
+        if not self.shard_grads:
+            raise RuntimeError("fused optimizer: unpack_shard_bucket() belongs to shard_grads=True")
+        gx = self._exchange()
+        params, slot, (rank, world) = self._layout()[1], gx["slot"], self._shard
+        if not 0 <= k < gx["n"]:
+            raise IndexError(f"fused optimizer: bucket {k} of {gx['n']}")
+        if gathered.dtype != torch.uint8 or gathered.numel() != world * slot or not gathered.is_contiguous():
+            raise ValueError(f"fused optimizer: unpack_shard_bucket() takes {world} x {slot} contiguous bytes")
+        _lib.require_device(gathered)
+        others = [(r, piece) for r, pieces in enumerate(gx["weight"][k]) if r != rank for piece in pieces]
+        table = (_lib.PrlSegment * max(len(others), 1))()
+        for seg, (r, (i, b, e, at)) in zip(table, others):
+            isz = params[i].element_size()
+            seg.tensor, seg.bucket_offset, seg.nbytes = params[i].data_ptr() + b * isz, r * slot + at, (e - b) * isz
+        _lib.check(_lib.load().prl_bucket_scatter(gathered.data_ptr(), gathered.numel(), table, len(others), _lib.current_stream_ptr(gathered.device)))
 
     # ---- segment table ----------------------------------------------------------------------------------------------------
     def _check_tensor(self, p: torch.Tensor, g: torch.Tensor | None) -> None:
@@ -644,7 +906,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
             g = self._grad_of(p)
             st = self.state[p] if g is not None else {}
             seg.param, seg.numel, seg.param_dtype = p.data_ptr() + b * p.element_size(), e - b, _DTYPES[p.dtype]
-            seg.grad = g.data_ptr() + b * g.element_size() if g is not None and p.numel() else None
+            at = 0 if self.shard_grads and p in self._acc_filled else b * g.element_size() if g is not None else 0  # a sharded accumulator IS the piece
+            seg.grad = g.data_ptr() + at if g is not None and p.numel() else None
             seg.grad_dtype = _DTYPES[g.dtype] if g is not None else _DTYPES[p.dtype]
             if g is not None:
                 self._fill_state(seg, st)
@@ -786,6 +1049,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._launch(lib, table, len(entries), self._record.data_ptr() if clipped else None)
         self._acc_filled.clear()  # the next fold of every accumulator overwrites
         self._reduced = False
+        self._folded = False
         if self._shard_group is not None:
             self._exchange_weights()
         return loss
@@ -831,6 +1095,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
     @torch.no_grad()
     def pack_shard(self) -> torch.Tensor:
         """This rank's pieces of the parameters, as they stand, packed into its send buffer (uint8, the same size on every rank)."""
+        self._no_whole_buffer("pack_shard() / unpack_shards()", "pack_shard_bucket(k) / unpack_shard_bucket(k, gathered) for k in range(n_grad_buckets())")
         _, size, send, _ = self._publish_buffers()
         _, out, n_out, _, _ = self._publish_tables()
         _lib.check(_lib.load().prl_bucket_gather(send.data_ptr(), size, out, n_out, _lib.current_stream_ptr(send.device)))
@@ -840,6 +1105,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def unpack_shards(self, gathered: torch.Tensor) -> None:
         """`gathered`: every rank's send buffer in rank order (world x size bytes); the other ranks' pieces are written into the
         parameters, the own ones are already there."""
+        self._no_whole_buffer("pack_shard() / unpack_shards()", "pack_shard_bucket(k) / unpack_shard_bucket(k, gathered) for k in range(n_grad_buckets())")
         _, size, _, _ = self._publish_buffers()
         _, _, _, inn, n_in = self._publish_tables()
         if gathered.dtype != torch.uint8 or gathered.numel() != self._shard[1] * size or not gathered.is_contiguous():
@@ -850,6 +1116,17 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def _exchange_weights(self) -> None:
         import torch.distributed as dist
 
+        if self.shard_grads:  # bucket by bucket through the exchange buffers: no whole-model receive buffer
+            gx = self._exchange()
+            nccl = dist.get_backend(self._shard_group) == "nccl"
+            for k in range(gx["n"]):
+                send = self.pack_shard_bucket(k)
+                if nccl:
+                    dist.all_gather_into_tensor(gx["recv"], send, group=self._shard_group)
+                else:
+                    dist.all_gather(list(gx["recv"].view(self._shard[1], -1).unbind(0)), send, group=self._shard_group)
+                self.unpack_shard_bucket(k, gx["recv"])
+            return
         _, _, _, recv = self._publish_buffers()
         send = self.pack_shard()
         if dist.get_backend(self._shard_group) == "nccl":
@@ -893,10 +1170,11 @@ class FusedAdamW(_FusedOptimizer):
 
     def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  master_weights: bool = True, grad_accum_dtype: torch.dtype | None = None, shard_group=None, shard: tuple[int, int] | None = None,
-                 state_dtype: torch.dtype | None = None, param_rounding: str = "nearest", seed: int = 0):
+                 state_dtype: torch.dtype | None = None, param_rounding: str = "nearest", seed: int = 0, shard_grads: bool = False,
+                 exchange_bucket_bytes: int = 64 << 20):
         _check_hyper(lr, betas, weight_decay, eps)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, seed=seed), master_weights, grad_accum_dtype, shard_group,
-                         shard, state_dtype, param_rounding)
+                         shard, state_dtype, param_rounding, shard_grads, exchange_bucket_bytes)
 
     def _launch_key(self, group):
         return (float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), int(group.get("seed", 0)))
@@ -916,10 +1194,11 @@ class FusedLion(_FusedOptimizer):
 
     def __init__(self, params, lr: float = 1e-4, betas: tuple[float, float] = (0.9, 0.99), weight_decay: float = 0.0, master_weights: bool = True,
                  grad_accum_dtype: torch.dtype | None = None, shard_group=None, shard: tuple[int, int] | None = None,
-                 state_dtype: torch.dtype | None = None, param_rounding: str = "nearest", seed: int = 0):
+                 state_dtype: torch.dtype | None = None, param_rounding: str = "nearest", seed: int = 0, shard_grads: bool = False,
+                 exchange_bucket_bytes: int = 64 << 20):
         _check_hyper(lr, betas, weight_decay)
         super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay, seed=seed), master_weights, grad_accum_dtype, shard_group, shard,
-                         state_dtype, param_rounding)
+                         state_dtype, param_rounding, shard_grads, exchange_bucket_bytes)
 
     def _launch_key(self, group):
         return (float(group["betas"][0]), float(group["betas"][1]), int(group.get("seed", 0)))
@@ -947,7 +1226,9 @@ class FusedAdafactor(_FusedOptimizer):
     def __init__(self, params, lr: float = 1e-3, eps1: float = 1e-30, clip_threshold: float = 1.0, decay_rate: float = -0.8, weight_decay: float = 0.0,
                  master_weights: bool = True, grad_accum_dtype: torch.dtype | None = None, beta1=None, relative_step: bool = False,
                  scale_parameter: bool = False, shard_group=None, shard: tuple[int, int] | None = None, state_dtype: torch.dtype | None = None,
-                 param_rounding: str = "nearest", seed: int = 0):
+                 param_rounding: str = "nearest", seed: int = 0, shard_grads: bool = False):
+        if shard_grads:
+            raise ValueError("FusedAdafactor: sharded gradients (shard_grads) are not built for Adafactor (it has no sharded state to go with them)")
         if state_dtype not in (None, torch.float32) or param_rounding != "nearest" or seed != 0:
             raise ValueError("FusedAdafactor: compact state (state_dtype, param_rounding, seed) is not built for Adafactor (its factored averages are tiny)")
         unsupported = [n for n, on in (("beta1", beta1 is not None), ("relative_step", relative_step), ("scale_parameter", scale_parameter)) if on]
@@ -1045,14 +1326,17 @@ class FusedAdafactor(_FusedOptimizer):
 
 def get_optimizer(name: str, model: torch.nn.Module, learning_rate: float, weight_decay: float, grad_accum_dtype: torch.dtype | None = None,
                   shard_group=None, shard: tuple[int, int] | None = None, state_dtype: torch.dtype | None = None, param_rounding: str = "nearest",
-                  seed: int = 0):
+                  seed: int = 0, shard_grads: bool = False, exchange_bucket_bytes: int = 64 << 20):
     """The reference's dispatch (:25-45) with its names; "adamw_torch" and "lion" are the fused HIP steps, "adafactor_hip" is the
     fused HIP form of "adafactor" (which stays transformers' class).
     `grad_accum_dtype=torch.float32`: fp32 gradient accumulation (the fused steps only); `shard_group` / `shard`: state sharded over
     the learner ranks ("adamw_torch" and "lion" only); `state_dtype` / `param_rounding` / `seed`: compact state with stochastic rounding
-    ("adamw_torch" and "lion" only)."""
+    ("adamw_torch" and "lion" only); `shard_grads` / `exchange_bucket_bytes`: the fp32 accumulators sharded like the state, gradients and
+    weights exchanged in buckets ("adamw_torch" and "lion" only)."""
     grouped_params = get_grouped_params(model, weight_decay)
-    compact = dict(state_dtype=state_dtype, param_rounding=param_rounding, seed=seed)
+    compact = dict(state_dtype=state_dtype, param_rounding=param_rounding, seed=seed, shard_grads=shard_grads, exchange_bucket_bytes=exchange_bucket_bytes)
+    if (shard_grads or exchange_bucket_bytes != 64 << 20) and name not in ("adamw_torch", "lion"):
+        raise ValueError(f'sharded gradients (shard_grads, exchange_bucket_bytes) need "adamw_torch" or "lion", not "{name}"')
     if (state_dtype not in (None, torch.float32) or param_rounding != "nearest" or seed != 0) and name not in ("adamw_torch", "lion"):
         raise ValueError(f'compact optimizer state (state_dtype, param_rounding, seed) needs "adamw_torch" or "lion", not "{name}"')
     if name == "adafactor_hip":

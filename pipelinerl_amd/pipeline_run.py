@@ -79,6 +79,7 @@ class PipelineSpec:
     optimizer: str = "adamw"           # "adamw" | "adamw_hip" (finetune/optim.py FusedAdamW) | "adafactor_hip" (FusedAdafactor) | "sgd" (parity tests)
     grad_accum_fp32: bool = False      # fold every micro-batch's gradients into fp32 accumulators (grad_accum_dtype=torch.float32 of the fused optimizers); needs "adamw_hip" or "adafactor_hip"
     shard_optimizer_state: bool = False  # ZeRO-1: each learner rank keeps the fused optimizer's fp32 state for 1/n_learners of the parameters (FusedAdamW(shard_group=...)); needs "adamw_hip"
+    shard_grad_accumulators: bool = False  # ZeRO-2: the fp32 accumulators sharded like the state, micro-batch gradients sent to their owners in buckets (FusedAdamW(shard_grads=True)); needs shard_optimizer_state and grad_accum_fp32
     param_dtype: str = "bf16"          # "bf16" (the reference's training dtype) | "fp32" (parity tests: tight parameter deltas)
     kl_coef: float = 0.0               # > 0 (configs[4]: 0.001): KL-to-reference on - the preprocessor holds the frozen reference policy (the initial policy) and writes `ref_logprobs`
     ref_seed: int | None = None        # seed of the reference policy (default: `seed`, i.e. the policy the run starts from)
@@ -113,6 +114,8 @@ class PipelineSpec:
             raise ValueError(f"grad_accum_fp32 folds gradients with the fused optimizer's kernel: it needs optimizer='adamw_hip' or 'adafactor_hip', not {self.optimizer!r}")
         if self.shard_optimizer_state and self.optimizer != "adamw_hip":
             raise ValueError(f"shard_optimizer_state partitions the fused optimizer's state: it needs optimizer='adamw_hip', not {self.optimizer!r}")
+        if self.shard_grad_accumulators and not (self.shard_optimizer_state and self.grad_accum_fp32):
+            raise ValueError("shard_grad_accumulators shards the fp32 gradient accumulators of the sharded optimizer: it needs shard_optimizer_state=True and grad_accum_fp32=True")
         if self.weight_transport not in ("ipc", "rccl", "gloo"):
             raise ValueError(f"weight_transport {self.weight_transport!r}: 'ipc', 'rccl' or 'gloo'")
         if self.weight_transport == "ipc" and not self.share_device:
@@ -607,7 +610,8 @@ def learner_stage(spec: PipelineSpec, rank: int = 0, name: str = "learner") -> N
         from .finetune.optim import FusedAdamW
 
         shard_group = torch.distributed.group.WORLD if spec.shard_optimizer_state and world > 1 else None  # one learner: nothing to shard
-        opt = FusedAdamW(train_model.parameters(), lr=spec.lr, grad_accum_dtype=torch.float32 if spec.grad_accum_fp32 else None, shard_group=shard_group)
+        opt = FusedAdamW(train_model.parameters(), lr=spec.lr, grad_accum_dtype=torch.float32 if spec.grad_accum_fp32 else None, shard_group=shard_group,
+                         shard_grads=spec.shard_grad_accumulators and shard_group is not None)
     else:
         opt = torch.optim.AdamW(train_model.parameters(), lr=spec.lr, fused=cuda)
     rl = rl_config_of(spec)

@@ -776,6 +776,32 @@ int prl_adafactor_step(const prl_adafactor_segment* segments, int64_t n_segments
                        prl_stream_t stream);
 int prl_adafactor_geometry(int64_t* band_rows, int64_t* tile_cols, int64_t* group_segments, int64_t* group_elements);
 
+/* ---- Fused body ops: RMSNorm and SwiGLU of a decoder layer (transformers' Qwen2RMSNorm / LlamaRMSNorm forward and
+ * `act_fn(gate_proj(x)) * up_proj(x)` of Qwen2MLP / LlamaMLP with hidden_act = "silu") ------------------------------------------
+ * RMSNorm over `rows` contiguous rows of `cols` elements; x and weight [cols] are fp32 or bf16 independently (PRL_DTYPE_*):
+ *   rstd[r] = 1 / sqrt(mean_c(x[r, c]^2) + eps)  (fp32 [rows]);   out[r, c] = weight[c] * (x[r, c] * rstd[r])
+ * in fp32 from the stored values, rounded once; `out` (and the `grad_out` that comes back for it) is bf16 when x AND weight are
+ * bf16, fp32 otherwise (torch's promotion of weight * x).  Backward, with xh = x * rstd:
+ *   grad_x[r, c] = rstd[r] * (g w - xh * mean_c(g w xh))   (dtype of x; nullable)
+ *   grad_weight[c] = sum_r g[r, c] xh[r, c]                 (fp32 [cols], overwritten; nullable)
+ * grad_weight goes through fp32 partials of 32-row bands in `workspace` (device, 16-byte aligned, prl_rmsnorm_workspace_bytes)
+ * that a second launch adds in band order: no atomics, every sum has a fixed order, two runs give the same bits.
+ * 16-byte moves when cols is a multiple of 8 (bf16 x) / 4 (fp32 x) and the arrays are 16-byte aligned; any other shape takes
+ * the same arithmetic one element at a time.  rows == 0 succeeds without a launch (grad_weight := 0).
+ * SwiGLU over `numel` contiguous elements, gate / up / out (and the three gradients) of one dtype:
+ *   out = silu(gate) * up,  silu(z) = z / (1 + exp(-z));   grad_up = g silu(gate);
+ *   grad_gate = g up s (1 + gate (1 - s)),  s = 1 / (1 + exp(-gate)).    numel == 0 succeeds without a launch.
+ * Arguments are validated before any device work; nothing allocates or synchronises. */
+int prl_rmsnorm_workspace_bytes(int64_t rows, int64_t cols, size_t* bytes);
+int prl_rmsnorm_fwd(int64_t rows, int64_t cols, const void* x, int32_t x_dtype, const void* weight, int32_t weight_dtype,
+                    float eps, void* out, float* rstd, prl_stream_t stream);
+int prl_rmsnorm_bwd(int64_t rows, int64_t cols, const void* x, int32_t x_dtype, const void* weight, int32_t weight_dtype,
+                    const float* rstd, const void* grad_out, void* grad_x, float* grad_weight, void* workspace,
+                    size_t workspace_bytes, prl_stream_t stream);
+int prl_swiglu_fwd(int64_t numel, const void* gate, const void* up, int32_t dtype, void* out, prl_stream_t stream);
+int prl_swiglu_bwd(int64_t numel, const void* gate, const void* up, const void* grad_out, int32_t dtype, void* grad_gate,
+                   void* grad_up, prl_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Fused output head: hidden states -> new_logprobs / entropy, logits never   */
 /* written (reference rl/__init__.py:204-233 after the model's */

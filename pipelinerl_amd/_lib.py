@@ -40,6 +40,17 @@ PRL_LM_HEAD_DW_OVERWRITE = 2
 PRL_LM_HEAD_DH_NO_WEIGHT_LO = 4
 PRL_LOG_CREATE, PRL_LOG_TRUNCATE, PRL_LOG_READER, PRL_LOG_TRIM = 1, 2, 4, 8
 
+# geometry of the fused body kernels (the PRL_BODY_* constants of csrc/prl_body_math.h; tests/test_body_api.py compares the two)
+BODY_GEOMETRY = {
+    "block": 256,           # threads per workgroup
+    "wave": 64,             # lanes that share one RMSNorm row
+    "rows_per_block": 4,    # RMSNorm forward / dx: one wave per row
+    "vec_bf16": 8,          # RMSNorm: elements per lane and iteration, bf16 x
+    "vec_f32": 4,           #          ... fp32 x
+    "band_rows": 32,        # RMSNorm dw: rows per band
+    "swiglu_vec": 8,        # SwiGLU: elements per thread
+}
+
 # index of every public statistic in the device stats vector (enum in include/prl.h)
 STAT_INDEX = {
     "loss": 0,
@@ -252,6 +263,11 @@ PROTOTYPES: dict[str, tuple] = {
     "prl_adafactor_workspace_bytes": (c_int32, [_P, c_int64, POINTER(c_size_t)]),
     "prl_adafactor_step": (c_int32, [_P, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, c_size_t, _P]),
     "prl_adafactor_geometry": (c_int32, [POINTER(c_int64)] * 4),
+    "prl_rmsnorm_workspace_bytes": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
+    "prl_rmsnorm_fwd": (c_int32, [c_int64, c_int64, _P, c_int32, _P, c_int32, c_float, _P, _P, _P]),
+    "prl_rmsnorm_bwd": (c_int32, [c_int64, c_int64, _P, c_int32, _P, c_int32, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "prl_swiglu_fwd": (c_int32, [c_int64, _P, _P, c_int32, _P, _P]),
+    "prl_swiglu_bwd": (c_int32, [c_int64, _P, _P, _P, c_int32, _P, _P, _P]),
     "prl_lm_head_prepare": (c_int32, [c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, _P]),
     "prl_lm_head_workspace_bytes": (c_int32, [c_int64, c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t), POINTER(c_size_t)]),
     "prl_lm_head_logprob_fwd": (c_int32, [c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_size_t, _P]),
@@ -289,7 +305,11 @@ def load() -> ctypes.CDLL:
 
     lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # an older build: additive changes keep the ABI version, so the number alone would not tell
+            raise ImportError(f"{path} does not export {name}: it was built from older sources; rebuild "
+                              "(`python -m pipelinerl_amd.build`)") from None
         fn.restype = restype
         fn.argtypes = argtypes
     got = lib.prl_abi_version()

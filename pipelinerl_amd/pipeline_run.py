@@ -75,6 +75,7 @@ class PipelineSpec:
     concurrent_groups: int = 4
     engine_load: bool = False          # the engine runs forward passes between updates (a colocated actor's GPU share)
     gradient_checkpointing: bool = False
+    fused_body: bool = False           # RMSNorm and SwiGLU of every decoder layer as single HIP launches (fused_body.install_fused_body)
     learner: str = "streamed"          # "streamed" (StreamedLearnerStep) or "dropin" (LearnerStep + rl_step_fused_head)
     optimizer: str = "adamw"           # "adamw" | "adamw_hip" (finetune/optim.py FusedAdamW) | "adafactor_hip" (FusedAdafactor) | "sgd" (parity tests)
     grad_accum_fp32: bool = False      # fold every micro-batch's gradients into fp32 accumulators (grad_accum_dtype=torch.float32 of the fused optimizers); needs "adamw_hip" or "adafactor_hip"
@@ -551,6 +552,12 @@ def learner_stage(spec: PipelineSpec, rank: int = 0, name: str = "learner") -> N
         rl_step_fn = rl_step_fused_head
     elif spec.learner == "streamed":
         raise ValueError("a hooked loss function drives LearnerStep: learner='dropin'")
+    if spec.fused_body:
+        from .fused_body import install_fused_body
+
+        install_fused_body(model)
+        _trace(spec, name, f"fused body: {model._prl_fused_body['rmsnorm']} norms, {model._prl_fused_body['swiglu']} MLPs, "
+                           f"{len(model._prl_fused_body['skipped'])} skipped")
     if spec.gradient_checkpointing:
         model.gradient_checkpointing_enable()
     model.train()

@@ -802,6 +802,38 @@ int prl_swiglu_fwd(int64_t numel, const void* gate, const void* up, int32_t dtyp
 int prl_swiglu_bwd(int64_t numel, const void* gate, const void* up, const void* grad_out, int32_t dtype, void* grad_gate,
                    void* grad_up, prl_stream_t stream);
 
+/* ---- Packed variable-length causal attention (what the reference gets from flash-attn's varlen path, driven by the
+ * position_ids resets of a packed batch; transformers' eager_attention_forward formula under a block-diagonal causal mask) ----
+ * The N = batch * t tokens of a batch lie flat.  prl_attn_segments writes, in one launch and with no copy to the host,
+ *   seq_start[i] = first token of i's sequence,  seq_end[i] = one past its last token         (int32 [N], device)
+ * where token i = b * t + c starts a sequence iff  c == 0,  or position_ids (int64 [N], nullable) has
+ * pos[i] != pos[i - 1] + 1,  or attention_mask ([N] of `mask_elem_bytes` = 1 (bool / uint8), 4 or 8 byte integers, nullable)
+ * has mask[i] == 0 or mask[i - 1] == 0: every pad token is a sequence of its own.  Key j is visible to query i iff
+ * seq_start[i] <= j <= i.
+ * Forward, bf16: q [N, hq, d], k and v [N, hkv, d] with token / head strides in elements (d contiguous, every row 16-byte
+ * aligned: strides are multiples of 8), d = 64 or 128, hq % hkv == 0, query head h reads KV head h / (hq / hkv):
+ *   s[i, j] = scale * q[i, h] . k[j, kv]     p[i, j] = exp(s[i, j] - lse[h, i])  over the visible j
+ *   lse[h, i] = ln sum_j exp(s[i, j])  (fp32 [hq, N])        out[i, h] = sum_j p[i, j] v[j, kv]   (bf16 [N, hq, d], contiguous)
+ * with fp32 accumulation and p rounded to bf16 once for the p v product.  Key blocks before seq_start of a query block are not
+ * read.  Backward, from grad_out (bf16 [N, hq, d], contiguous), out and lse, with delta[h, i] = sum_d grad_out . out (fp32, in
+ * `workspace`: device, 16-byte aligned, prl_attn_workspace_bytes; its contents on entry do not matter):
+ *   dp = grad_out v^T    ds = p (dp - delta)    grad_q = scale ds k    grad_k = scale ds^T q    grad_v = p^T grad_out
+ * grad_q [N, hq, d], grad_k and grad_v [N, hkv, d], bf16, contiguous; the hq / hkv query heads of a KV head are added in
+ * index order.  Three launches, no atomics: every sum has one fixed order, two runs give the same bits.
+ * Arguments are validated before any device work; N == 0 succeeds without a launch; nothing allocates or synchronises. */
+int prl_attn_segments(int64_t batch, int64_t t, const int64_t* position_ids, const void* attention_mask,
+                      int32_t mask_elem_bytes, int32_t* seq_start, int32_t* seq_end, prl_stream_t stream);
+int prl_attn_workspace_bytes(int64_t n, int64_t hq, size_t* bytes);
+int prl_attn_varlen_fwd(int64_t n, int64_t hq, int64_t hkv, int64_t d, const void* q, int64_t q_stride_t,
+                        int64_t q_stride_h, const void* k, int64_t k_stride_t, int64_t k_stride_h, const void* v,
+                        int64_t v_stride_t, int64_t v_stride_h, float scale, const int32_t* seq_start,
+                        const int32_t* seq_end, void* out, float* lse, prl_stream_t stream);
+int prl_attn_varlen_bwd(int64_t n, int64_t hq, int64_t hkv, int64_t d, const void* q, int64_t q_stride_t,
+                        int64_t q_stride_h, const void* k, int64_t k_stride_t, int64_t k_stride_h, const void* v,
+                        int64_t v_stride_t, int64_t v_stride_h, float scale, const int32_t* seq_start,
+                        const int32_t* seq_end, const void* out, const float* lse, const void* grad_out, void* grad_q,
+                        void* grad_k, void* grad_v, void* workspace, size_t workspace_bytes, prl_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Fused output head: hidden states -> new_logprobs / entropy, logits never   */
 /* written (reference rl/__init__.py:204-233 after the model's */

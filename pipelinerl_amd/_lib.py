@@ -268,6 +268,11 @@ PROTOTYPES: dict[str, tuple] = {
     "prl_rmsnorm_bwd": (c_int32, [c_int64, c_int64, _P, c_int32, _P, c_int32, _P, _P, _P, _P, _P, c_size_t, _P]),
     "prl_swiglu_fwd": (c_int32, [c_int64, _P, _P, c_int32, _P, _P]),
     "prl_swiglu_bwd": (c_int32, [c_int64, _P, _P, _P, c_int32, _P, _P, _P]),
+    # packed varlen causal attention
+    "prl_attn_segments": (c_int32, [c_int64, c_int64, _P, _P, c_int32, _P, _P, _P]),
+    "prl_attn_workspace_bytes": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
+    "prl_attn_varlen_fwd": (c_int32, [c_int64] * 4 + [_P, c_int64, c_int64] * 3 + [c_float, _P, _P, _P, _P, _P]),
+    "prl_attn_varlen_bwd": (c_int32, [c_int64] * 4 + [_P, c_int64, c_int64] * 3 + [c_float, _P, _P] + [_P] * 7 + [c_size_t, _P]),
     "prl_lm_head_prepare": (c_int32, [c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, _P]),
     "prl_lm_head_workspace_bytes": (c_int32, [c_int64, c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t), POINTER(c_size_t)]),
     "prl_lm_head_logprob_fwd": (c_int32, [c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_size_t, _P]),

@@ -45,6 +45,7 @@ SOURCES = [
     "prl_optim_compact.hip",
     "prl_adafactor.hip",
     "prl_body.hip",
+    "prl_attention.hip",
     "prl_lmhead_prepare.hip",
     "prl_lmhead_fwd.hip",
     "prl_lmhead_bwd.hip",

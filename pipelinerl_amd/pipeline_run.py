@@ -76,6 +76,7 @@ class PipelineSpec:
     engine_load: bool = False          # the engine runs forward passes between updates (a colocated actor's GPU share)
     gradient_checkpointing: bool = False
     fused_body: bool = False           # RMSNorm and SwiGLU of every decoder layer as single HIP launches (fused_body.install_fused_body)
+    fused_attention: bool = False      # packed varlen causal attention: packed sequences kept apart (fused_attention.install_fused_attention)
     learner: str = "streamed"          # "streamed" (StreamedLearnerStep) or "dropin" (LearnerStep + rl_step_fused_head)
     optimizer: str = "adamw"           # "adamw" | "adamw_hip" (finetune/optim.py FusedAdamW) | "adafactor_hip" (FusedAdafactor) | "sgd" (parity tests)
     grad_accum_fp32: bool = False      # fold every micro-batch's gradients into fp32 accumulators (grad_accum_dtype=torch.float32 of the fused optimizers); needs "adamw_hip" or "adafactor_hip"
@@ -558,6 +559,12 @@ def learner_stage(spec: PipelineSpec, rank: int = 0, name: str = "learner") -> N
         install_fused_body(model)
         _trace(spec, name, f"fused body: {model._prl_fused_body['rmsnorm']} norms, {model._prl_fused_body['swiglu']} MLPs, "
                            f"{len(model._prl_fused_body['skipped'])} skipped")
+    if spec.fused_attention:
+        from .fused_attention import install_fused_attention
+
+        install_fused_attention(model)
+        _trace(spec, name, f"fused attention: {model._prl_fused_attention['layers']} layers (was {model._prl_fused_attention['previous']}), "
+                           f"{len(model._prl_fused_attention['skipped'])} on the sdpa fallback")
     if spec.gradient_checkpointing:
         model.gradient_checkpointing_enable()
     model.train()

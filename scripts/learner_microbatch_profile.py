@@ -2,7 +2,10 @@
 synthetic rollouts packed into `--budget`-token micro-batches): host wall clock per micro-batch next to the device time of its
 phases (HIP events: body forward, head forward + K2/K3, head backward, body backward), for several packing budgets.
 
-    python scripts/learner_microbatch_profile.py [--budgets 2048,4096,8192,16384] [--samples 64] [--model 0p5b] [--fused-body]
+    python scripts/learner_microbatch_profile.py [--budgets 2048,4096,8192,16384] [--samples 64] [--model 0p5b] [--fused-body] [--fused-attention]
+
+Without --fused-attention the body runs stock sdpa, which attends a packed micro-batch as ONE sequence (every later sequence sees the
+earlier ones): that figure times a path that mixes sequences.  With it the packed sequences are kept apart, as in the reference.
 """
 
 import argparse
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--gradient-checkpointing", action="store_true")
     ap.add_argument("--fused-body", action="store_true", help="RMSNorm and SwiGLU through pipelinerl_amd.fused_body")
     ap.add_argument("--fused-body-ops", default="rmsnorm,swiglu", help="with --fused-body: which of the two ops are installed")
+    ap.add_argument("--fused-attention", action="store_true", help="packed varlen attention through pipelinerl_amd.fused_attention")
     ap.add_argument("--repeats", type=int, default=1, help="measured passes per budget; the reported pass is the one with the median wall clock")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -45,6 +49,10 @@ def main():
 
         ops = a.fused_body_ops.split(",")
         install_fused_body(model, rmsnorm="rmsnorm" in ops, swiglu="swiglu" in ops)
+    if a.fused_attention:
+        from pipelinerl_amd.fused_attention import install_fused_attention
+
+        install_fused_attention(model)
     if a.gradient_checkpointing:
         model.gradient_checkpointing_enable()
     model.train()
@@ -111,7 +119,9 @@ def main():
         def span(x, y):
             return sum(p.elapsed_time(q) for p, q in zip(marks[x], marks[y])) / n
 
-        res = {"budget": budget, "fused_body": a.fused_body_ops if a.fused_body else False, "repeats": len(passes),
+        res = {"budget": budget, "fused_body": a.fused_body_ops if a.fused_body else False,
+               "attention": "prl_varlen (packed sequences kept apart)" if a.fused_attention else "stock sdpa (a packed micro-batch is attended as one sequence)",
+               "repeats": len(passes),
                "wall_ms_per_micro_batch_all_passes": [1e3 * p[0] / n for p in passes], "micro_batches": n, "tokens": tok, "tokens_per_micro_batch": tok / n,
                "wall_ms_per_micro_batch": 1e3 * wall / n, "host_issue_ms_per_micro_batch": 1e3 * host_s / n, "us_per_token": 1e6 * wall / tok,
                "device_ms": {"body_forward": span("body_fwd_begin", "body_fwd_end"), "head_forward_and_loss": span("body_fwd_end", "loss_ready"),

@@ -168,6 +168,8 @@ class _VarlenAttnFn(torch.autograd.Function):
         n, hq, d = qc.shape
         hkv = kc.shape[1]
         g = grad_out.contiguous()
+        if g.data_ptr() % 16:  # (a contiguous slice of a flat buffer: the kernels read whole 16-byte pieces of rows)
+            g = g.clone()
         dq = torch.empty((n, hq, d), dtype=torch.bfloat16, device=qc.device)
         dk = torch.empty((n, hkv, d), dtype=torch.bfloat16, device=qc.device)
         dv = torch.empty((n, hkv, d), dtype=torch.bfloat16, device=qc.device)

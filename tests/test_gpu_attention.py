@@ -1,6 +1,7 @@
 """The packed varlen attention kernels on the GPU: the segment kernel against `segments()` on the CPU bit for bit; forward and
-backward against the fp64 witness under the per-entry bounds of tests/attention_checks.py; isolation of packed sequences, two
-runs, skipped key blocks and the workspace bit for bit."""
+backward against the fp64 witness under the per-entry bounds of tests/attention_checks.py (4 x the error of the flash
+arithmetic on the CPU); isolation of packed sequences, two runs, the layouts of the upstream gradient, the scale as an argument,
+skipped key blocks and the workspace bit for bit."""
 
 import ctypes
 
@@ -138,7 +139,7 @@ def test_strided_view_and_copied_layout_give_the_same_bits(libprl, cuda_device):
 
 
 # ---- isolation, bit for bit ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["edges", "b2"])  # boundaries one before / on / one after a block edge and inside a block
+@pytest.mark.parametrize("name", ["edges", "b2", "mid"])  # boundaries one before / on / one after a block edge and inside a block; "mid": mask-free tiles beyond it
 def test_other_sequences_do_not_reach_a_sequence(libprl, cuda_device, name):
     case, (hq, hkv), d = CASES[name], (4, 2), 64
     q, k, v, g, scale = ac.inputs(case, hq, hkv, d)
@@ -160,11 +161,67 @@ def test_other_sequences_do_not_reach_a_sequence(libprl, cuda_device, name):
 
 
 def test_two_runs_give_the_same_bits(libprl, cuda_device):
-    for name, heads, d in (("edges", (7, 1), 128), ("long", (4, 2), 64)):
+    for name, heads, d in (("edges", (7, 1), 128), ("long", (4, 2), 64), ("mid_ramp", (4, 2), 128)):
         case = CASES[name]
         q, k, v, g, scale = ac.inputs(case, heads[0], heads[1], d)
         ss, se = ac.table_of(case.lengths)
         same_bits(run(q, k, v, g, ss, se, scale, cuda_device), run(q, k, v, g, ss, se, scale, cuda_device), what=f"{name}: second run")
+
+
+def test_upstream_gradient_layouts_give_the_same_bits(libprl, cuda_device):
+    """The upstream gradient as a contiguous tensor, as a transposed view of head-major memory, as a slice of a wider buffer (its
+    data_ptr() is not the start of an allocation) and as the expanded stride-0 tensor of `out.sum().backward()`: the same values
+    give the same dq, dk, dv bit for bit."""
+    case, (hq, hkv), d = CASES["edges"], (4, 2), 64
+    q, k, v, g, scale = ac.inputs(case, hq, hkv, d)
+    ss, se = (t.to(cuda_device) for t in ac.table_of(case.lengths))
+    n = case.n
+    gd = g.to(device=cuda_device, dtype=torch.bfloat16)
+
+    def go(upstream):
+        qd, kd, vd = (t.to(device=cuda_device, dtype=torch.bfloat16).requires_grad_(True) for t in (q, k, v))
+        out, lse = varlen_attention(qd, kd, vd, ss, se, scale, return_lse=True)
+        upstream(out)
+        torch.cuda.synchronize(cuda_device)
+        return {"out": out.detach().cpu(), "lse": lse.cpu(), "dq": qd.grad.cpu(), "dk": kd.grad.cpu(), "dv": vd.grad.cpu()}
+
+    base = go(lambda out: out.backward(gd))
+    ac.check_outputs("edges", "contiguous upstream gradient", base, ac.witness(q, k, v, g, ss.cpu(), scale))
+
+    head_major = gd.transpose(0, 1).contiguous()  # [Hq, N, D]
+    view = head_major.transpose(0, 1)
+    assert not view.is_contiguous() and torch.equal(view, gd)
+    same_bits(base, go(lambda out: out.backward(view)), what="a transposed view as the upstream gradient")
+
+    wide = torch.zeros(n + 3, hq, d + 8, dtype=torch.bfloat16, device=cuda_device)
+    wide[3:, :, 8:] = gd
+    piece = wide[3:, :, 8:]
+    assert piece.data_ptr() != wide.data_ptr() and not piece.is_contiguous() and torch.equal(piece, gd)
+    same_bits(base, go(lambda out: out.backward(piece)), what="a slice of a wider buffer as the upstream gradient")
+    for shift in (8, 4):  # contiguous, 16 and 8 bytes into its allocation: read where it lies / copied once to 16-byte alignment
+        shifted = torch.zeros(n * hq * d + shift, dtype=torch.bfloat16, device=cuda_device)[shift:].view(n, hq, d)
+        shifted.copy_(gd)
+        assert shifted.is_contiguous() and shifted.data_ptr() % 32 == 2 * shift
+        same_bits(base, go(lambda out: out.backward(shifted)), what=f"a contiguous upstream gradient {2 * shift} bytes into an allocation")
+
+    ones = go(lambda out: out.backward(torch.ones_like(out)))
+    same_bits(ones, go(lambda out: out.sum().backward()), what="the expanded stride-0 gradient of out.sum()")
+    assert not torch.equal(ones["dq"], base["dq"])
+
+
+def test_scale_is_an_argument(libprl, cuda_device):
+    """scale and 2 x scale with q halved (exact in bf16): the products scale q . k are the same numbers, so out, lse, dk and dv are
+    the same bits and dq is exactly twice (tests/test_attention_checks_host.py shows the flash arithmetic does just that).  A
+    kernel with the scale fixed in one of its uses breaks one of them."""
+    case, (hq, hkv), d = CASES["b2"], (4, 2), 64
+    q, k, v, g, scale = ac.inputs(case, hq, hkv, d)
+    ss, se = ac.table_of(case.lengths)
+    assert torch.equal(ac.bf16_exact(0.5 * q), 0.5 * q)
+    a = run(q, k, v, g, ss, se, scale, cuda_device)
+    b = run(0.5 * q, k, v, g, ss, se, 2.0 * scale, cuda_device)
+    ac.check_outputs("b2", "scale as given", a, ac.witness(q, k, v, g, ss, scale))
+    twice = dict(a, dq=(2.0 * a["dq"].float()).to(torch.bfloat16))  # (a doubling is exact in bf16)
+    same_bits(twice, b, what="scale doubled and q halved")
 
 
 def test_key_blocks_before_the_sequence_start_are_not_read(libprl, cuda_device):

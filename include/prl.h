@@ -834,6 +834,36 @@ int prl_attn_varlen_bwd(int64_t n, int64_t hq, int64_t hkv, int64_t d, const voi
                         const int32_t* seq_end, const void* out, const float* lse, const void* grad_out, void* grad_q,
                         void* grad_k, void* grad_v, void* workspace, size_t workspace_bytes, prl_stream_t stream);
 
+/* ---- The sequence-parallel slice form (what the reference gets from ring_flash_attn's all-gather-K/V varlen attention) ----
+ * A packed row of nk tokens is cut into contiguous slices, one per rank.  A rank holds the nq queries of its slice - local
+ * query i is global token q_off + i - and the k, v (bf16 [nk, hkv, d], strided as above), seq_start, seq_end (int32 [nk]) of
+ * the WHOLE gathered row.  Key j is visible to local query i iff seq_start[q_off + i] <= j <= q_off + i.
+ * Forward: out [nq, hq, d] bf16 contiguous, lse fp32 [hq, nq].  Key tiles lie on the global 64-grid and the sweep of a query
+ * block starts at the tile that holds its first query's seq_start: keys before it and keys from q_off + nq on are never read.
+ * With q_off a multiple of 64 the tiles and sum orders are those of prl_attn_varlen_fwd / _bwd on the whole row, and out, lse
+ * and grad_q are its rows bit for bit.
+ * Backward: grad_q [nq, hq, d] bf16, and grad_k_part, grad_v_part: fp32 [nk, hkv, d], contiguous, this slice's share of the
+ * sums grad_k / grad_v of the whole row (the hq / hkv query heads of a KV head, then the local queries, in index order).
+ * Every element of both is written: exact zeros for the rows no local query can see.  They are fp32 because the shares of the
+ * P ranks are added before the single rounding:
+ *   prl_attn_fold_parts:  out[e] = bf16_rne(parts[0][e] + parts[1][e] + ... + parts[P - 1][e])   parts fp32 [P, n_elems]
+ * contiguous, the sum in fp32 in rank order, out bf16 [n_elems]; both 16-byte aligned.
+ * `workspace` (delta fp32 [hq, nq]): prl_attn_slice_workspace_bytes.  No atomics; two runs give the same bits.  Arguments are
+ * validated before any device work (0 <= q_off, q_off + nq <= nk, P >= 1, and everything the square form checks);
+ * nq == 0 and n_elems == 0 succeed without a launch (and write nothing). */
+int prl_attn_slice_workspace_bytes(int64_t nq, int64_t hq, size_t* bytes);
+int prl_attn_slice_fwd(int64_t nq, int64_t nk, int64_t q_off, int64_t hq, int64_t hkv, int64_t d, const void* q,
+                       int64_t q_stride_t, int64_t q_stride_h, const void* k, int64_t k_stride_t, int64_t k_stride_h,
+                       const void* v, int64_t v_stride_t, int64_t v_stride_h, float scale, const int32_t* seq_start,
+                       const int32_t* seq_end, void* out, float* lse, prl_stream_t stream);
+int prl_attn_slice_bwd(int64_t nq, int64_t nk, int64_t q_off, int64_t hq, int64_t hkv, int64_t d, const void* q,
+                       int64_t q_stride_t, int64_t q_stride_h, const void* k, int64_t k_stride_t, int64_t k_stride_h,
+                       const void* v, int64_t v_stride_t, int64_t v_stride_h, float scale, const int32_t* seq_start,
+                       const int32_t* seq_end, const void* out, const float* lse, const void* grad_out, void* grad_q,
+                       float* grad_k_part, float* grad_v_part, void* workspace, size_t workspace_bytes,
+                       prl_stream_t stream);
+int prl_attn_fold_parts(int64_t p, int64_t n_elems, const float* parts, void* out, prl_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Fused output head: hidden states -> new_logprobs / entropy, logits never   */
 /* written (reference rl/__init__.py:204-233 after the model's */

@@ -273,6 +273,11 @@ PROTOTYPES: dict[str, tuple] = {
     "prl_attn_workspace_bytes": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
     "prl_attn_varlen_fwd": (c_int32, [c_int64] * 4 + [_P, c_int64, c_int64] * 3 + [c_float, _P, _P, _P, _P, _P]),
     "prl_attn_varlen_bwd": (c_int32, [c_int64] * 4 + [_P, c_int64, c_int64] * 3 + [c_float, _P, _P] + [_P] * 7 + [c_size_t, _P]),
+    # ... its sequence-parallel slice form: nq local queries at q_off against the nk keys of the gathered row
+    "prl_attn_slice_workspace_bytes": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
+    "prl_attn_slice_fwd": (c_int32, [c_int64] * 6 + [_P, c_int64, c_int64] * 3 + [c_float, _P, _P, _P, _P, _P]),
+    "prl_attn_slice_bwd": (c_int32, [c_int64] * 6 + [_P, c_int64, c_int64] * 3 + [c_float, _P, _P] + [_P] * 7 + [c_size_t, _P]),
+    "prl_attn_fold_parts": (c_int32, [c_int64, c_int64, _P, _P, _P]),
     "prl_lm_head_prepare": (c_int32, [c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, _P]),
     "prl_lm_head_workspace_bytes": (c_int32, [c_int64, c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t), POINTER(c_size_t)]),
     "prl_lm_head_logprob_fwd": (c_int32, [c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_size_t, _P]),

@@ -46,6 +46,7 @@ SOURCES = [
     "prl_adafactor.hip",
     "prl_body.hip",
     "prl_attention.hip",
+    "prl_attention_sp.hip",
     "prl_lmhead_prepare.hip",
     "prl_lmhead_fwd.hip",
     "prl_lmhead_bwd.hip",

@@ -22,97 +22,15 @@
 // row, dK^T / dV^T never leave the accumulators.  (3) dQ: a workgroup per query block x query head sweeps the forward's keys and
 // recomputes S and dP.  Seven products instead of five: the price of sums with one fixed order and no hand-off between workgroups.
 // A finished 64 x D tile goes through LDS and leaves as whole 16-byte pieces of rows.
-#include "prl_common.h"
-#include "prl_optim_math.h"
-#include "prl_osm.h"
-
 #define PRL_ATTN_BQ 64
 #define PRL_ATTN_BK 64
+#include "prl_attention_core.h"  // staging, fragments, the tile store, the delta row sum: shared with prl_attention_sp.hip
 
 namespace {
 
-using prl::osm::fast_exp2;
-using prl::osm::kLn2;
-using prl::osm::kLog2e;
-using prl::osm::kNegBig;
+using namespace prl::attn;
 
-constexpr int kBlk = 64;        // rows of a block and of a swept tile (PRL_ATTN_BQ == PRL_ATTN_BK)
-constexpr int kThreads = 256;   // 4 waves x 16 rows
-constexpr int kLdT = kBlk + 8;  // row length of a [.][64] LDS image: 144 bytes, 16-byte multiple, rows fall on different banks
 constexpr int kSegThreads = 1024;
-constexpr float kVisible = -1.0e38f;  // a score above this is a visible one (masked ones are kNegBig)
-static_assert(PRL_ATTN_BQ == kBlk && PRL_ATTN_BK == kBlk, "one tile size");
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-__host__ __device__ inline int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
-
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ bf16x8 lds_frag(const uint16_t* img, int ld, int row, int col) {
-  return as_frag(*reinterpret_cast<const u32x4*>(img + row * ld + col));
-}
-__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float max16(float v) {  // over the 16 lanes that share a C row
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float sum16(float v) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Rows [r0, r0 + 64) of one head of a [N, H, D] array (src points at the head, st = token stride) into the row image
-// rows[64][D + 8] and / or the transposed image cols[D][64 + 8].  A row outside [lo, hi) reads as zero and is not touched.
-template <int D, bool ROWS, bool COLS>
-__device__ __forceinline__ void stage(const uint16_t* __restrict__ src, int64_t st, int64_t r0, int64_t lo, int64_t hi, uint16_t* rows, uint16_t* cols) {
-  constexpr int CH = D / 8;
-  for (int i = threadIdx.x; i < kBlk * CH; i += kThreads) {
-    const int row = i / CH, ch = i % CH;
-    const int64_t g = r0 + row;
-    u32x4 val = {0u, 0u, 0u, 0u};
-    if (g >= lo && g < hi) val = *reinterpret_cast<const u32x4*>(src + g * st + ch * 8);
-    if constexpr (ROWS) *reinterpret_cast<u32x4*>(rows + row * (D + 8) + ch * 8) = val;
-    if constexpr (COLS) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) cols[(ch * 8 + e) * kLdT + row] = uint16_t(val[e >> 1] >> ((e & 1) * 16));
-    }
-  }
-}
-
-// The 16 rows of this wave as A fragments straight from global memory: lane (g, c) takes row0 + c, columns 32 kk + 8 g ..
-template <int D>
-__device__ __forceinline__ void row_frags(const uint16_t* __restrict__ src, int64_t st, int64_t row, int64_t n, int g, bf16x8 (&a)[D / 32]) {
-#pragma unroll
-  for (int kk = 0; kk < D / 32; ++kk) {
-    u32x4 val = {0u, 0u, 0u, 0u};
-    if (row < n) val = *reinterpret_cast<const u32x4*>(src + row * st + kk * 32 + g * 8);
-    a[kk] = as_frag(val);
-  }
-}
-
-// acc (this wave's 16 rows x D, C layout) x mul -> bf16 rows [16 w ..] of the image, then whole rows to dst [N, H, D] (dst at the head)
-template <int D>
-__device__ __forceinline__ void store_tile(const f32x4 (&acc)[D / 16], const float (&mul)[4], uint16_t* img, uint16_t* __restrict__ dst, int64_t st,
-                                           int64_t r0, int64_t n) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
-  __syncthreads();  // the image's last readers are done
-#pragma unroll
-  for (int t = 0; t < D / 16; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) img[(16 * w + 4 * g + r) * (D + 8) + 16 * t + c] = prl_f32_to_bf16_rne(acc[t][r] * mul[r]);
-  __syncthreads();
-  constexpr int CH = D / 8;
-  for (int i = threadIdx.x; i < kBlk * CH; i += kThreads) {
-    const int row = i / CH, ch = i % CH;
-    const int64_t gr = r0 + row;
-    if (gr < n) *reinterpret_cast<u32x4*>(dst + gr * st + ch * 8) = *reinterpret_cast<const u32x4*>(img + row * (D + 8) + ch * 8);
-  }
-}
 
 // ---- segment table -----------------------------------------------------------------------------------------------------------
 // One workgroup per batch row; a thread owns a run of consecutive tokens.  Pass 1 finds the last and the first sequence start of
@@ -209,6 +127,7 @@ __global__ __launch_bounds__(kThreads) void attn_fwd_kernel(const uint16_t* __re
       for (int kk = 0; kk < D / 32; ++kk) s[nn] = mfma(qa[kk], lds_frag(k_rows, LDD, 16 * nn + c, 32 * kk + 8 * g), s[nn]);
     }
     const bool whole = k0 >= ss_last && k0 + kBlk - 1 <= q0;  // inside one sequence, below the diagonal
+    // (softmax_step of prl_attention_core.h, written out: this kernel compiles to the schedule it had before the step was shared)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float y[4];
@@ -253,28 +172,11 @@ __global__ __launch_bounds__(kThreads) void attn_fwd_kernel(const uint16_t* __re
 }
 
 // ---- backward 1: delta = rowsum(dO * O) ----------------------------------------------------------------------------------------
-// D / 8 lanes per (token, head) row, 16 bytes each; a lane's 8 products pairwise, the lanes by butterfly: one fixed order.
+// (delta_rows of prl_attention_core.h: one fixed order.)
 template <int D>
 __global__ __launch_bounds__(kThreads) void attn_delta_kernel(const uint16_t* __restrict__ o, const uint16_t* __restrict__ d_o, float* __restrict__ delta,
                                                               int64_t n, int hq) {
-  constexpr int L = D / 8;
-  const int64_t r = (int64_t(blockIdx.x) * kThreads + threadIdx.x) / L;  // row = t * hq + h (whole groups of L lanes share a row)
-  const int part = threadIdx.x % L;
-  float acc = 0.0f;
-  if (r < n * hq) {
-    const u32x4 a = *reinterpret_cast<const u32x4*>(o + r * D + part * 8);
-    const u32x4 b = *reinterpret_cast<const u32x4*>(d_o + r * D + part * 8);
-    float p[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      p[2 * e] = __uint_as_float(a[e] << 16) * __uint_as_float(b[e] << 16);
-      p[2 * e + 1] = __uint_as_float(a[e] & 0xffff0000u) * __uint_as_float(b[e] & 0xffff0000u);
-    }
-    acc = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-  }
-#pragma unroll
-  for (int off = 1; off < L; off <<= 1) acc = acc + __shfl_xor(acc, off, 64);
-  if (r < n * hq && part == 0) delta[(r % hq) * n + r / hq] = acc;
+  delta_rows<D>(o, d_o, delta, n, hq);
 }
 
 // ---- backward 2: dK, dV ----------------------------------------------------------------------------------------------------------
@@ -436,27 +338,6 @@ __global__ __launch_bounds__(kThreads) void attn_dq_kernel(const uint16_t* __res
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-constexpr int64_t kMaxTokens = (int64_t(1) << 31) - 2 * kBlk;  // token indices and block starts fit int32
-
-int check_shape(int64_t n, int64_t hq, int64_t hkv, int64_t d) {
-  PRL_CHECK_ARG(n >= 0, "negative n %lld", (long long)n);
-  PRL_CHECK_ARG(n <= kMaxTokens, "n %lld tokens do not fit the int32 segment table", (long long)n);
-  PRL_CHECK_ARG(d == 64 || d == 128, "head size %lld: the kernels are built for 64 and 128", (long long)d);
-  PRL_CHECK_ARG(hq > 0 && hkv > 0 && hq <= 65535, "heads (hq %lld, hkv %lld) must be positive and at most 65535", (long long)hq, (long long)hkv);
-  PRL_CHECK_ARG(hq % hkv == 0, "hq %lld is not a multiple of hkv %lld", (long long)hq, (long long)hkv);
-  return PRL_OK;
-}
-
-int check_operand(const char* name, const void* p, int64_t st, int64_t sh, int64_t d) {
-  PRL_CHECK_ARG(p != nullptr, "%s is null", name);
-  PRL_CHECK_ARG(prl::aligned16(p), "%s is not 16-byte aligned", name);
-  PRL_CHECK_ARG(st >= d && sh >= 0, "%s: token stride %lld must be at least d and head stride %lld not negative", name, (long long)st, (long long)sh);
-  PRL_CHECK_ARG(st % 8 == 0 && sh % 8 == 0, "%s: strides (%lld, %lld) break the 16-byte alignment of its rows", name, (long long)st, (long long)sh);
-  return PRL_OK;
-}
-
-size_t workspace_need(int64_t n, int64_t hq) { return size_t((n * hq * 4 + 15) & ~int64_t(15)); }
-
 }  // namespace
 
 extern "C" int prl_attn_segments(int64_t batch, int64_t t, const int64_t* position_ids, const void* attention_mask, int32_t mask_elem_bytes,

@@ -650,6 +650,12 @@ class LearnerStep(_LearnerBase):
         self.rl_step_fn = rl_step_fn
         self.seq_parallel_group = seq_parallel_group
         self.seq_parallel = seq_parallel
+        # The reference calls update_ring_flash_attn_params(batch.seq_boundaries, group) before every micro-batch (finetune_loop.py:517,
+        # 757-759).  Here the group is bound once, by install_fused_attention(model, seq_parallel_group=group), and the gathered
+        # position_ids carry the boundaries; a model whose attention is not bound would attend each slice alone, so it is refused.
+        from .fused_attention import require_seq_parallel_attention
+
+        require_seq_parallel_attention(model, seq_parallel_group)
         self.max_train_steps = max_train_steps
         self.max_lag = max_lag
         self.train_batch_size = train_batch_size
